@@ -1,7 +1,21 @@
 """Benchmark of the hot path: the fused SDE rollout on the BASELINE synthetic shape.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
+
+A plain run does only what the headline needs: it draws the 5 batches, warms up, times the K
+launches, writes the last timed launch's outputs if --dump-outputs is given, and prints the
+line (metric, value, ms_per_step, roofline of the same wall clock).  Everything else takes
+runs of its own and is measured only with --full: `strong_scaling`, `speedup_vs_1`, the
+`variants` (in-kernel Philox, the device sampler, float64, TD1 assembly, the fused NN rollout,
+the training iterations) and `cpu_baseline`; --no-variants / --no-train / --no-cpu-baseline
+leave parts of a --full run out, and --mall / --strong-proxy, which ask for one more variant
+each, turn --full on.
+--dump-outputs DIR writes what the last timed launch computed, x [N+1,B',d], dt [B',N] and
+coef [B',N], as DIR/x.npy, DIR/dt.npy and DIR/coef.npy in the run's dtype: rank 0's batch,
+cut to a fixed seeded sample of B' = 2048 (f32) or 1024 (f64) of its 4096 trajectories (36 MB
+in all; dump_sample_index).  The inputs come from the device sampler with fixed seeds, so two
+runs with the same arguments write the same arrays.
 
 Both forms run N ranks: without a launcher around it, `--gpus N > 1` starts
 torch.distributed.run as a child process (before any GPU call) and relays rank 0's line.
@@ -21,7 +35,7 @@ MALL-resident) is the variant `rollout_mall_resident`, run only with --mall: it 
 same kernel, and without it every launch of the headline kernel in a default run is a cold
 one, so a rocprofv3 summary of the driver's command averages exactly the headline's launches.
 Trajectories shard across ranks by global index (weak scaling, no collective on
-the data path).  Beside the weak-scaling headline the line carries `strong_scaling` (the same
+the data path).  Beside the weak-scaling headline a --full line carries `strong_scaling` (the same
 rollout with the GLOBAL batch fixed at 4096 and split over the ranks by parallel.shard_range,
 SURVEY §8(d)) and `speedup_vs_1`: both figures divided by the one-GPU figure, which rank 0
 measures alone inside the same job (the other ranks wait at a barrier), so the driver's 1->8
@@ -141,6 +155,24 @@ class RolloutSets:
             if rc:
                 raise self.err("dpac_rollout_fwd", rc, self.lib.dpac_last_error().decode())
         return launch
+
+
+def dump_sample_index(B, esize):
+    """The trajectories --dump-outputs keeps: a fixed, seeded sample (sorted) of 2048 (f32) or
+    1024 (f64) of the batch's B, so the three arrays stay at 36 MB (x alone is 66 MB in f32)."""
+    keep = min(B, 2048 * 4 // esize)
+    return np.sort(np.random.default_rng(4096).choice(B, keep, replace=False))
+
+
+def dump_outputs(path, bufs, esize):
+    """Write one buffer set's outputs (what dpac_rollout_fwd's caller receives: x, dt, coef),
+    cut to dump_sample_index's trajectories, as path/<name>.npy in the run's dtype."""
+    _, _, x, dt, coef = bufs
+    idx = torch.as_tensor(dump_sample_index(x.shape[1], esize), device=x.device)
+    os.makedirs(path, exist_ok=True)
+    arrays = {"x": x.index_select(1, idx), "dt": dt.index_select(0, idx), "coef": coef.index_select(0, idx)}
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
 
 
 def training_variant(name, dtype, B, world=1, iters=6, warmup=3, par=None, total=None):
@@ -425,14 +457,24 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--dtype", choices=["f32", "f64"], default="f32")
     ap.add_argument("--scheme", choices=["adaptive", "naive"], default="adaptive")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-variants", action="store_true")
-    ap.add_argument("--no-train", action="store_true", help="skip the training-iteration variants")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed launch's outputs (a fixed sample of rank 0's "
+                         "trajectories) as DIR/x.npy, DIR/dt.npy, DIR/coef.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure strong scaling, the one-GPU reference, the variants and the "
+                         "CPU baseline (a plain run times the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the variants")
+    ap.add_argument("--no-train", action="store_true",
+                    help="with --full: skip the training-iteration variants")
     ap.add_argument("--strong-proxy", action="store_true",
-                    help="also time the strong-scaling shards (B = 4096 / 2, 4, 8) on this one GPU")
+                    help="--full, and also time the strong-scaling shards (B = 4096 / 2, 4, 8) on this one GPU")
     ap.add_argument("--mall", action="store_true",
-                    help="also time the MALL-resident one-set loop (same kernel as the headline)")
+                    help="--full, and also time the MALL-resident one-set loop (same kernel as the headline)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    args.full = args.full or args.mall or args.strong_proxy
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -472,22 +514,27 @@ def main():
     ms_per_step = wall / args.steps * 1e3
     value = world * B * N * args.steps / wall
     algo_bytes = B * N * (2 * d + 2) * esize
-    # the one-GPU figure of the same job: rank 0 alone (the others wait at a barrier), the same
-    # B = 4096 batch, launches and timer; at N = 1 it is the headline itself
-    if world > 1:
-        barrier(world)
-        if rank == 0:
-            progress("one-GPU reference: rank 0 alone")
-            solo_wall, _ = time_launches(rs.launcher(N_SETS), args.steps, args.warmup, 1)
-            solo_value = B * N * args.steps / solo_wall
+    if args.dump_outputs and rank == 0:
+        # the set the last timed launch (i = K - 1) wrote, before anything launches over it again
+        dump_outputs(args.dump_outputs, rs.sets[(args.steps - 1) % N_SETS], esize)
+    strong = solo_value = None
+    if args.full:
+        # the one-GPU figure of the same job: rank 0 alone (the others wait at a barrier), the same
+        # B = 4096 batch, launches and timer; at N = 1 it is the headline itself
+        if world > 1:
+            barrier(world)
+            if rank == 0:
+                progress("one-GPU reference: rank 0 alone")
+                solo_wall, _ = time_launches(rs.launcher(N_SETS), args.steps, args.warmup, 1)
+                solo_value = B * N * args.steps / solo_wall
+            else:
+                solo_value = 0.0
+            barrier(world)
+            solo_value = max_over_ranks(solo_value, world)
         else:
-            solo_value = 0.0
-        barrier(world)
-        solo_value = max_over_ranks(solo_value, world)
-    else:
-        solo_value = value
-    strong = strong_scaling(lib, eqp, scheme, dtype, rank, world, args, value, ms_per_step, esize,
-                            solo_value)
+            solo_value = value
+        strong = strong_scaling(lib, eqp, scheme, dtype, rank, world, args, value, ms_per_step, esize,
+                                solo_value)
     # the same timer as `value`: the wall clock over the K launches (max over ranks) / K
     achieved = algo_bytes / (ms_per_step * 1e-3) / 1e9
     achieved_ev = algo_bytes / (per_launch_ms * 1e-3) / 1e9
@@ -508,13 +555,7 @@ def main():
                      "external" if world > 1 else None),
                  "note": ("ranks share a GPU: DPAC_DIST_BACKEND=gloo rehearsal, not a scaling figure"
                           if shared else "one rank per GPU")},
-        "strong_scaling": strong,
-        "speedup_vs_1": {"weak": value / solo_value, "strong": strong["value"] / solo_value,
-                         "one_gpu_value": solo_value, "unit": "traj-steps/s",
-                         "note": "one_gpu_value: B = 4096 on ONE GPU (rank 0 alone inside this job, the "
-                                 "same launches and wall timer; at N = 1 the headline itself); weak = "
-                                 "value / one_gpu_value (B = 4096 per GPU), strong = strong_scaling.value / "
-                                 "one_gpu_value (B = 4096 in all)"},
+        "full": args.full,
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                      "traffic_source": tsrc, "kernel": "dpac::k_rollout_staged",
@@ -528,7 +569,15 @@ def main():
                              "HBM-cold one, so rocprofv3 --stats of the same command averages them "
                              "(tools/rocprof_headline.py -> profiles/r06_rocprof_headline.json)"},
     }
-    if not args.no_variants:
+    if args.full:
+        out["strong_scaling"] = strong
+        out["speedup_vs_1"] = {"weak": value / solo_value, "strong": strong["value"] / solo_value,
+                               "one_gpu_value": solo_value, "unit": "traj-steps/s",
+                               "note": "one_gpu_value: B = 4096 on ONE GPU (rank 0 alone inside this job, the "
+                                       "same launches and wall timer; at N = 1 the headline itself); weak = "
+                                       "value / one_gpu_value (B = 4096 per GPU), strong = strong_scaling.value / "
+                                       "one_gpu_value (B = 4096 in all)"}
+    if args.full and not args.no_variants:
         progress("variants: in-kernel Philox, float64, TD1, fused NN rollout" + (", MALL-resident" if args.mall else ""))
         variants = {}
         k2 = max(20, args.steps // 4)
@@ -690,10 +739,10 @@ def main():
             v["speedup_vs_1"] = one_ms / v["ms_per_iteration"]
             variants["training_dp_lqr_var_d20"] = v
         out["variants"] = variants
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         progress("cpu_baseline (oracle on the host cores, bounded samples)")
         out["cpu_baseline"] = cpu_baseline()
-    elif rank == 0:
+    elif args.full and rank == 0:
         out["cpu_baseline"] = None
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -43,8 +43,8 @@ case "${1:-check}" in
     bash tools/profile_round.sh
     ;;
   dp)
-    run 300 bench1 python -u bench.py --steps 50 --warmup 5 --no-cpu-baseline
-    DPAC_DIST_BACKEND=gloo run 300 bench2_gloo python -u bench.py --gpus 2 --steps 20 --warmup 3
+    run 300 bench1 python -u bench.py --steps 50 --warmup 5 --full --no-cpu-baseline
+    DPAC_DIST_BACKEND=gloo run 300 bench2_gloo python -u bench.py --gpus 2 --steps 20 --warmup 3 --full
     ;;
   seeds)
     bash tools/seed_spread.sh "$2"

@@ -14,7 +14,7 @@ if [ -z "${SKIP_TESTS:-}" ]; then
   run 900 pytest_gpu python -u -m pytest tests -m gpu -q -p no:cacheprovider --timeout 120 --timeout-method thread
   run 300 smoke python -u -c "import __graft_entry__ as g; g.smoke()"
 fi
-run 400 bench python -u bench.py --steps 200 --warmup 20
+run 400 bench python -u bench.py --steps 200 --warmup 20 --full
 # the driver's exact command under the profiler (its --stats AverageNs of the headline kernel is
 # the mean over exactly the W + K headline launches: the MALL variant runs only with --mall)
 run 400 prof_kt rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof_kt -o run --output-format csv -- python bench.py --gpus 1 --steps 20 --warmup 5
