@@ -14,6 +14,8 @@
 #include <rocrand/rocrand_kernel.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "dpac.h"
 #include "dpac_mfma.h"
 
@@ -336,6 +338,19 @@ __device__ __forceinline__ T group_shift_in(T keep, T v, bool group_start) {
     if constexpr (P < 16) sh = group_start ? v : sh;
     return sh;
   }
+}
+
+// Pin values at this point of the program: an empty volatile asm per value.  Volatile asms and
+// memory operations keep their program order, so the instructions that produce a pinned value
+// come before, and the ones that use it after, everything pinned or stored later.
+template <typename T>
+__device__ __forceinline__ void pin(T& v) {
+  asm volatile("" : "+v"(v));
+}
+template <typename T, typename... Ts>
+__device__ __forceinline__ void pin(T& v, Ts&... more) {
+  pin(v);
+  pin(more...);
 }
 
 template <int P>
@@ -834,5 +849,14 @@ struct EqVDP {
     }
   }
 };
+
+// Equations whose sigma() reads neither the state nor the control: the staged rollout scales the
+// next step's increments by it ahead of the step.
+template <class E>
+struct ConstSigma : std::false_type {};
+template <typename T, int D, int P>
+struct ConstSigma<EqLQR<T, D, P>> : std::true_type {};
+template <typename T, int D, int P>
+struct ConstSigma<EqEKN<T, D, P>> : std::true_type {};
 
 }  // namespace dpac

@@ -15,6 +15,7 @@
 #pragma once
 
 #include <cmath>
+#include <limits>
 #include <type_traits>
 #include <utility>
 
@@ -505,6 +506,10 @@ __global__ __launch_bounds__(64) void k_rollout(const E eq, const DevConsts<T> c
 constexpr int kStCW = 4;   // compute wavefronts per workgroup
 constexpr int kStCH = 16;  // steps per hand-off chunk
 constexpr int kStPD = DPAC_ST_PD;
+#ifndef DPAC_ST_STEP
+#define DPAC_ST_STEP 1  // 1: k_rollout_staged's own step body, below; 0 (timing knob): Transition, as in k_rollout
+#endif
+constexpr bool kOwnStep = DPAC_ST_STEP != 0;
 static_assert(kStPD >= 1 && kStPD <= kStCH, "prefetch distance within a chunk");
 template <typename T, int D, int P>
 struct StagedPlan {
@@ -556,6 +561,52 @@ constexpr int st_waves() { return kStCW + (GEN > 0 ? GEN : 1); }
 #endif
 constexpr int kStGen = DPAC_ST_GEN;
 
+// Timing-only builds (-DDPAC_ST_TRACE=1, like DPAC_NN_TRACE): lane 0 of every wavefront of the
+// first and the last workgroup stores the shader clock (low 32 bits) at fixed points of
+// k_rollout_staged into a per-TU device table, read back by dpac_debug_staged_trace
+// (tools/probe_staged_trace.py).  Row layout, kStTraceRow words per (workgroup, wavefront):
+//   0 entry, 1 after the barrier, 2 x0 loaded, 3 first chunk seen ready, 4 the last store issued
+//   (loader: after its last publish), 7 every store acknowledged, 5 / 6 the 100 MHz real-time
+//   clock at entry / at the end;
+//   16 + c  chunk c: compute waves start it (ready seen); loader starts issuing it
+//   48 + c  chunk c: compute waves finish it; loader has issued it
+//   80 + c  chunk c: cycles the compute waves polled `ready`; loader: when it published in pass c
+#ifndef DPAC_ST_TRACE
+#define DPAC_ST_TRACE 0
+#endif
+#if DPAC_ST_TRACE
+constexpr int kStTraceRow = 128, kStTraceWaves = 16, kStTraceChunks = 32;
+static __device__ uint32_t g_st_trace[2 * kStTraceWaves * kStTraceRow];  // [first | last workgroup][wave][point]
+__device__ __forceinline__ uint32_t st_clock() {
+  unsigned long long t;
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+  __builtin_amdgcn_sched_barrier(0);
+  return (uint32_t)t;
+}
+__device__ __forceinline__ uint32_t st_realtime() {
+  unsigned long long t;
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+  __builtin_amdgcn_sched_barrier(0);
+  return (uint32_t)t;
+}
+#define ST_PUT(pt, v)                \
+  do {                               \
+    const uint32_t st_v_ = (v);      \
+    if (st_on) st_row[(pt)] = st_v_; \
+  } while (0)
+#define ST_MARK(pt) ST_PUT(pt, st_clock())
+#define ST_CHUNK(base, c0) ((base) + ((c0) / kStCH < kStTraceChunks ? (c0) / kStCH : kStTraceChunks - 1))
+#else
+#define ST_PUT(pt, v) \
+  do {                \
+  } while (0)
+#define ST_MARK(pt) \
+  do {              \
+  } while (0)
+#endif
+
 template <typename T, class E, int D, int SCHEME, int OUT, int KB, int GEN = 0>
 __global__ __launch_bounds__(64 * st_waves<GEN>()) void k_rollout_staged(const E eq, const DevConsts<T> c,
                                                                           const RolloutArgs<T> a) {
@@ -573,6 +624,12 @@ __global__ __launch_bounds__(64 * st_waves<GEN>()) void k_rollout_staged(const E
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x / 64), lane = (int)threadIdx.x % 64;
   const int64_t row0 = xcd_block(blockIdx.x, gridDim.x) * TPW;
   const int N = a.N;
+#if DPAC_ST_TRACE
+  const bool st_on = lane == 0 && wave < kStTraceWaves && (blockIdx.x == 0 || blockIdx.x == gridDim.x - 1);
+  uint32_t* const st_row = g_st_trace + ((blockIdx.x == 0 ? 0 : kStTraceWaves) + (wave < kStTraceWaves ? wave : 0)) * kStTraceRow;
+  ST_MARK(0);
+  ST_PUT(5, st_realtime());
+#endif
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int w = 0; w < NREADY; ++w) s_ready[w] = 0;
@@ -582,6 +639,7 @@ __global__ __launch_bounds__(64 * st_waves<GEN>()) void k_rollout_staged(const E
   if (threadIdx.x < RS * 4)  // the zero pads (lanes that own no component read them)
     reinterpret_cast<uint32_t*>(s_ring + (threadIdx.x / 4) * SLOT_LDS + PL::PADOFF)[threadIdx.x % 4] = 0u;
   __syncthreads();
+  ST_MARK(1);
 
   if constexpr (GEN > 0) {
     if (wave >= kStCW) {  // ---- generator g: its share of each chunk's counter blocks -> the ring ----
@@ -649,6 +707,9 @@ __global__ __launch_bounds__(64 * st_waves<GEN>()) void k_rollout_staged(const E
         }
       }
       asm volatile("" ::: "memory");
+#if DPAC_ST_TRACE
+      ST_MARK(ST_CHUNK(16, c0));
+#endif
 #pragma unroll
       for (int s = 0; s < kStCH; ++s) {
         const int t = c0 + s < N ? c0 + s : N - 1;  // past the end: re-copy the last step (unused)
@@ -668,14 +729,22 @@ __global__ __launch_bounds__(64 * st_waves<GEN>()) void k_rollout_staged(const E
           }
         }
       }
+#if DPAC_ST_TRACE
+      ST_MARK(ST_CHUNK(48, c0));
+#endif
       // the previous chunk has landed once only this chunk's copies are outstanding
       if (c0 > 0) {
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kStCH * PIECES) : "memory");
         if (lane == 0) lds_store_relaxed(&s_ready[0], c0);
+#if DPAC_ST_TRACE
+        ST_MARK(ST_CHUNK(80, c0));
+#endif
       }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (lane == 0) lds_store_relaxed(&s_ready[0], N);
+    ST_MARK(4);
+    ST_PUT(6, st_realtime());
     return;
   }
 
@@ -711,6 +780,22 @@ __global__ __launch_bounds__(64 * st_waves<GEN>()) void k_rollout_staged(const E
   T r = TR::kRadius ? dsqrt(Lanes<P>::sum(sumsq(x))) : T(0);
   Flags fl = SCHEME == DPAC_SCHEME_ADAPTIVE ? region(r, c) : Flags{true, false};
   T disc = 1, y = 0;
+  // the own step's state (see `step` below): the candidate chain xc / rc, the radius Ra the
+  // chain measures against (R while the trajectory runs, -inf once it is dead), whether it runs
+  // (naive scheme), the step's dt and sqrt(dt), and sqrt(dt0) as the hardware computes it
+  T xc[M], rc = r;
+#pragma unroll
+  for (int m = 0; m < M; ++m) xc[m] = x[m];
+  T Ra = fl.alive ? c.R : -std::numeric_limits<T>::infinity();
+  bool alive = fl.alive;
+  const T sq0 = SCHEME == DPAC_SCHEME_ADAPTIVE ? dsqrt(c.dt0) : c.sqrt_dt0;
+  T dt = c.dt0, sq = sq0;
+  if constexpr (kOwnStep && SCHEME == DPAC_SCHEME_ADAPTIVE) {
+    dt = adaptive_dt_raw(fl.layer, r, c);
+    dt = fl.layer ? fmax(dt, c.dt_min) : dt;
+    sq = dsqrt(dt);
+  }
+  ST_MARK(2);  // the clock read waits for nothing of x0; r's DPP sum above did
   // slot_bytes: (t % RS) * SLOT_LDS, formed once per chunk plus a compile-time step offset
   auto read_dw_at = [&](int t, uint32_t slot_bytes, T (&dwv)[M]) {  // components past d read 0
     if constexpr (kVecRead) {
@@ -750,8 +835,82 @@ __global__ __launch_bounds__(64 * st_waves<GEN>()) void k_rollout_staged(const E
       flush(t, F);
     }
   };
+  // The staged kernel's own step (DPAC_ST_STEP = 1): Transition's arithmetic, bit for bit, laid out
+  // for a lone wavefront, whose time per step is the length of its dependent chain (the clock
+  // trace, DESIGN section 4: 233 cycles for 36 instructions).  What the chain keeps is
+  //   sum -> sqrt -> R - rt -> (b b) / den -> max -> sqrt -> select -> (sigma dw) sqrt(dt) -> fma -> add -> sumsq;
+  //  * the candidate state is the chain's state: xc = xt, unselected.  While the trajectory runs,
+  //    x == xc bit for bit; once a step is rejected the trajectory is dead for good, Ra = -inf
+  //    makes every later b = Ra - rt fail both compares, and whatever xc drifts to (inf and NaN
+  //    included) reaches no output: x, r, u and the cost are taken from the selected state, dt and
+  //    coef from the compares;
+  //  * the next step's dt comes from the candidate radius: dt' = layer' ? max((b b) / den, dt_min)
+  //    : dt0 with b = R - rt.  layer' implies coef, so whenever the boundary-layer value is used
+  //    r' == rt and b is the b of Transition's second subtraction; a dead trajectory steps with dt0;
+  //  * sqrt(dt') is selected from sqrt(boundary-layer dt) and sqrt(dt0), both the hardware square
+  //    root of the value Transition would take it of, so the root leaves the compare's shadow.
+  // The selects of x and r, the stores and the dt / coef shift register hang off the chain.
+  auto step = [&](int t, const T (&dwv)[M], auto phase) {
+    T uc[MC], f[M], s[M], xt[M];
+    eq.u_true(xc, rc, uc);
+    eq.drift(xc, uc, rc, f);
+    eq.sigma(xc, uc, s);
+#pragma unroll
+    for (int m = 0; m < M; ++m) xt[m] = xc[m] + fma(f[m], dt, (s[m] * dwv[m]) * sq);  // as Transition
+    const T St = Lanes<P>::sum(sumsq(xt));
+    T u[MC];  // the control at the selected state (frozen once dead): an output and the cost's input
+    if constexpr (COST || WANT_U) eq.u_true(x, r, u);
+    bool coef;
+    T rt = T(0), dtn = dt, sqn = sq;
+    if constexpr (SCHEME == DPAC_SCHEME_ADAPTIVE) {
+      rt = dsqrt(St);
+      const T b = Ra - rt;  // R - rt while the trajectory runs: region(rt) and adaptive_dt_raw(rt) share it
+      const bool inner = b - c.c_layer > T(0);
+      coef = b > T(0);
+      const T dtb = fmax((b * b) * c.inv_den, c.dt_min);
+      const T sqb = dsqrt(dtb);
+      const bool layer = coef && !inner;
+      dtn = layer ? dtb : c.dt0;
+      sqn = layer ? sqb : sq0;
+      Ra = coef ? Ra : -std::numeric_limits<T>::infinity();
+    } else {
+      if constexpr (E::kNeedsNorm) rt = dsqrt(St);
+      coef = alive && !(St - c.R2 >= T(0));
+      alive = coef;
+    }
+    if constexpr (COST) {
+      const T cf = coef ? T(1) : T(0);
+      const T w = eq.w_finish(Lanes<P>::sum(eq.w_part(x, u)));
+      y += cost_increment(a.cost_order, w, cf, dt, disc);
+      disc = disc * disc_factor(dt, cf, c);
+    }
+    const T kv = coef ? dt : -dt;
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+      x[m] = coef ? xt[m] : x[m];
+      xc[m] = xt[m];
+    }
+    if constexpr (E::kNeedsNorm) {
+      r = coef ? rt : r;
+      rc = rt;
+    }
+    dt = dtn;
+    sq = sqn;
+    sx.template store<DPAC_ROLLOUT_X_AUX>(rs_x, x, (uint32_t)(t + 1) * slab);
+    if constexpr (WANT_U) su.store(rs_u, u, (uint32_t)t * slab_u);
+    constexpr int PH = decltype(phase)::value;
+    keep = group_shift_in<P>(keep, kv, lc.p == 0);
+    if constexpr (PH >= 0) {
+      if constexpr (PH % F == F - 1) flush(t, F);
+    } else if ((t & (F - 1)) == F - 1) {
+      flush(t, F);
+    }
+  };
   for (int c0 = 0; c0 < N; c0 += kStCH) {
     const int want = c0 + kStCH < N ? c0 + kStCH : N;
+#if DPAC_ST_TRACE
+    const uint32_t st_poll0 = st_clock();
+#endif
     for (;;) {  // every producer has published the chunk
       int mn = lds_load_relaxed(&s_ready[0]);
 #pragma unroll
@@ -760,6 +919,14 @@ __global__ __launch_bounds__(64 * st_waves<GEN>()) void k_rollout_staged(const E
       __builtin_amdgcn_s_sleep(1);
     }
     asm volatile("" ::: "memory");
+#if DPAC_ST_TRACE
+    {
+      const uint32_t st_now = st_clock();
+      ST_PUT(ST_CHUNK(16, c0), st_now);
+      ST_PUT(ST_CHUNK(80, c0), st_now - st_poll0);
+      if (c0 == 0) ST_PUT(3, st_now);
+    }
+#endif
     if (c0 + kStCH <= N) {
       // RS is a multiple of kStCH: the chunk's slots are contiguous from cb
       const uint32_t cb = (uint32_t)__builtin_amdgcn_readfirstlane((c0 % RS) * SLOT_LDS);
@@ -774,21 +941,36 @@ __global__ __launch_bounds__(64 * st_waves<GEN>()) void k_rollout_staged(const E
         for (int m = 0; m < M; ++m) cur[m] = nxt[S % PD][m];
         if constexpr (S + PD < kStCH) read_dw_at(c0 + S + PD, cb + (uint32_t)((S + PD) * SLOT_LDS), nxt[S % PD]);
         if constexpr (PD > 1) __builtin_amdgcn_sched_barrier(0);  // issue the read here, PD steps ahead
-        body(c0 + S, cur, Phase<S>{});
+        if constexpr (kOwnStep)
+          step(c0 + S, cur, Phase<S>{});
+        else
+          body(c0 + S, cur, Phase<S>{});
       };
       unroll_phases(one, std::make_integer_sequence<int, kStCH>{});
     } else {
       for (int t = c0; t < N; ++t) {
         T cur[M];
         read_dw(t, cur);
-        body(t, cur, Phase<-1>{});
+        if constexpr (kOwnStep)
+          step(t, cur, Phase<-1>{});
+        else
+          body(t, cur, Phase<-1>{});
       }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (lane == 0) lds_store_relaxed(&s_done[wave], want);
+#if DPAC_ST_TRACE
+    ST_MARK(ST_CHUNK(48, c0));
+#endif
   }
   const int rem = N & (F - 1);
   if (rem) flush(N - 1, rem);
+#if DPAC_ST_TRACE
+  ST_MARK(4);  // every store issued (not yet acknowledged)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  ST_MARK(7);  // every store acknowledged
+  ST_PUT(6, st_realtime());
+#endif
   if constexpr (COST) {
     if (lc.live && lc.p == 0) {
       a.y[lc.b] = y;
