@@ -500,17 +500,20 @@ __global__ __launch_bounds__(64) void k_rollout(const E eq, const DevConsts<T> c
 #ifndef DPAC_ST_TIGHT_CHUNKS
 #define DPAC_ST_TIGHT_CHUNKS 3  // hand-off chunks of a ring of 16-byte-aligned slots
 #endif
-#ifndef DPAC_ST_PD
-#define DPAC_ST_PD 1  // compute waves: steps of dw read from the ring ahead of use
+#ifndef DPAC_ST_PREFETCH
+// compute waves: 1 a whole chunk's dw read into registers at the chunk's top and an unrolled
+// remainder, where the instantiation takes it (kChunkRegs, below); 0 (timing knob) every
+// instantiation reads one step ahead of use and runs a rolled remainder loop
+#define DPAC_ST_PREFETCH 1
 #endif
 constexpr int kStCW = 4;   // compute wavefronts per workgroup
 constexpr int kStCH = 16;  // steps per hand-off chunk
-constexpr int kStPD = DPAC_ST_PD;
+constexpr int kStPrefetch = DPAC_ST_PREFETCH;
+static_assert(kStPrefetch == 0 || kStPrefetch == 1, "DPAC_ST_PREFETCH is 0 or 1");
 #ifndef DPAC_ST_STEP
 #define DPAC_ST_STEP 1  // 1: k_rollout_staged's own step body, below; 0 (timing knob): Transition, as in k_rollout
 #endif
 constexpr bool kOwnStep = DPAC_ST_STEP != 0;
-static_assert(kStPD >= 1 && kStPD <= kStCH, "prefetch distance within a chunk");
 template <typename T, int D, int P>
 struct StagedPlan {
   static constexpr int TPW = kStCW * (64 / P);                                   // trajectories per workgroup
@@ -906,6 +909,19 @@ __global__ __launch_bounds__(64 * st_waves<GEN>()) void k_rollout_staged(const E
       flush(t, F);
     }
   };
+  // A chunk's dw in registers (kChunkRegs): all kStCH steps' ring reads are issued together at
+  // the chunk's top and the compiler places counted lgkmcnt waits in front of the steps that use
+  // them, so a step waits for LDS only where its own read has not returned; the last N % kStCH
+  // steps run as unrolled pieces.  A chunk is kStCH M dwords per lane in float, twice that in
+  // double.  Which instantiations read this way is decided by the compiler's resource remarks
+  // (profiles/staged_prefetch_resources_*.txt) and by measurement:
+  //  * not with the cost outputs: given a chunk in registers the scheduler fills the register
+  //    budget of these larger bodies and spills (float generator variant: 25 VGPRs; double: 5 to 30);
+  //  * not the generator variant: its compute wave shares the SIMD with three generator
+  //    wavefronts, which hide the LDS latency already (128 VGPRs, 16 wavefronts per workgroup);
+  //  * the others (dw from memory, one compute wavefront per SIMD, 256 VGPRs) do.
+  // The rest read each step's dw one step ahead of its use and run a rolled remainder loop.
+  constexpr bool kChunkRegs = kStPrefetch != 0 && !COST && GEN == 0;
   for (int c0 = 0; c0 < N; c0 += kStCH) {
     const int want = c0 + kStCH < N ? c0 + kStCH : N;
 #if DPAC_ST_TRACE
@@ -927,10 +943,48 @@ __global__ __launch_bounds__(64 * st_waves<GEN>()) void k_rollout_staged(const E
       if (c0 == 0) ST_PUT(3, st_now);
     }
 #endif
-    if (c0 + kStCH <= N) {
+    if constexpr (kChunkRegs) {
+      // steps t0 .. t0 + count - 1 (count <= kStCH, inside one chunk, whose slots are contiguous
+      // in the ring: RS is a multiple of kStCH): all reads, then the steps at compile-time phases
+      auto steps = [&](int t0, auto count) {
+        constexpr int CNT = decltype(count)::value;
+        const uint32_t cb = (uint32_t)__builtin_amdgcn_readfirstlane((t0 % RS) * SLOT_LDS);
+        T dwv[CNT][M];
+#pragma unroll
+        for (int q = 0; q < CNT; ++q) read_dw_at(t0 + q, cb + (uint32_t)(q * SLOT_LDS), dwv[q]);
+        auto one = [&](auto sidx) {
+          constexpr int S = decltype(sidx)::value;
+          if constexpr (kOwnStep)
+            step(t0 + S, dwv[S], Phase<S>{});
+          else
+            body(t0 + S, dwv[S], Phase<S>{});
+        };
+        unroll_phases(one, std::make_integer_sequence<int, CNT>{});
+      };
+      if (c0 + kStCH <= N) {
+        steps(c0, Phase<kStCH>{});
+      } else {
+        // The remainder as unrolled pieces of 8, 4, 2 and 1 steps.  A piece of L steps starts at
+        // a multiple of 2 L past c0 and the flush period F is a power of two: for F <= 2 L the
+        // flush phase of step s of the piece is s % F, and for F > 2 L no step of the piece
+        // flushes and s < F - 1, so Phase<s> is right either way.
+        static_assert(kStCH == 16, "remainder pieces of 8, 4, 2 and 1 steps");
+        int t0 = c0;
+        auto piece = [&](auto len) {
+          if ((N - c0) & decltype(len)::value) {
+            steps(t0, len);
+            t0 += decltype(len)::value;
+          }
+        };
+        piece(Phase<8>{});
+        piece(Phase<4>{});
+        piece(Phase<2>{});
+        piece(Phase<1>{});
+      }
+    } else if (c0 + kStCH <= N) {
       // RS is a multiple of kStCH: the chunk's slots are contiguous from cb
       const uint32_t cb = (uint32_t)__builtin_amdgcn_readfirstlane((c0 % RS) * SLOT_LDS);
-      constexpr int PD = kStPD;  // steps of dw in registers ahead of use
+      constexpr int PD = 1;  // steps of dw in registers ahead of use
       T nxt[PD][M];
 #pragma unroll
       for (int q = 0; q < PD; ++q) read_dw_at(c0 + q, cb + (uint32_t)(q * SLOT_LDS), nxt[q]);
@@ -940,7 +994,6 @@ __global__ __launch_bounds__(64 * st_waves<GEN>()) void k_rollout_staged(const E
 #pragma unroll
         for (int m = 0; m < M; ++m) cur[m] = nxt[S % PD][m];
         if constexpr (S + PD < kStCH) read_dw_at(c0 + S + PD, cb + (uint32_t)((S + PD) * SLOT_LDS), nxt[S % PD]);
-        if constexpr (PD > 1) __builtin_amdgcn_sched_barrier(0);  // issue the read here, PD steps ahead
         if constexpr (kOwnStep)
           step(c0 + S, cur, Phase<S>{});
         else

@@ -54,7 +54,7 @@ def main():
     assert nch <= CHUNKS
     print(f"# k_rollout_staged clock trace: {a.dtype} {a.scheme} LQR d={d} B={B} N={N}, launch {a.launches} of "
           f"{a.launches} over {bench.N_SETS} cold buffer sets; cycles of the shader clock since the wave's entry")
-    per_step = []
+    per_step, period, handoff, tail = [], [], [], []
     for g, gname in enumerate(("first workgroup", "last workgroup")):
         t0 = tr[g, 0, 0]
         rt = rel(tr[g, 0, 6], tr[g, 0, 5])  # 100 MHz ticks, compute wave 0
@@ -80,6 +80,11 @@ def main():
                 line += "%8d %6d %5d  " % (s, e, p)
                 if c < full and c >= 1:
                     per_step.append((e - s) / CH)
+                if 2 <= c < full:  # chunk 1 may still wait for the loader
+                    period.append((s - rel(r[16 + c - 1], t0)) / CH)
+                    handoff.append(s - rel(r[48 + c - 1], t0))
+                if c == full and N % CH:
+                    tail.append(e - s)
             r = tr[g, 4]
             line += "%13d %6d %7s" % (rel(r[16 + c], t0), rel(r[48 + c], t0), rel(r[80 + c], t0) if r[80 + c] else "-")
             print(line)
@@ -87,6 +92,16 @@ def main():
     print(f"\nsteady state (full chunks 1..{full - 1}, both workgroups, 4 compute waves): "
           f"median {np.median(ps):.1f} cycles/step, min {ps.min():.1f}, max {ps.max():.1f} "
           f"(includes the two stamps per chunk, about 40 cycles each: -5 cycles/step)")
+    if period:
+        pe, ho = np.array(period), np.array(handoff)
+        print(f"chunk period (start of chunk c - 1 to start of chunk c, c = 2..{full - 1}, hand-off and stamps "
+              f"included): median {np.median(pe):.1f} cycles/step, min {pe.min():.1f}, max {pe.max():.1f}")
+        print(f"hand-off (end stamp of chunk c - 1, after its `done` publish, to start stamp of chunk c, "
+              f"after the `ready` poll): median {np.median(ho):.0f} cycles, min {ho.min()}, max {ho.max()}")
+    if tail:
+        ta = np.array(tail)
+        print(f"last {N % CH} steps (the remainder after {full} full chunks): median {np.median(ta):.0f} cycles, "
+              f"min {ta.min()}, max {ta.max()} = {np.median(ta) / (N % CH):.1f} cycles/step")
     w0 = tr[:, :4]
     poll = w0[:, :, 80:80 + nch].astype(np.int64)
     print(f"ready polls: chunk 0 median {np.median(poll[:, :, 0]):.0f} cycles, later chunks median "
