@@ -2,7 +2,7 @@
 # and needs no build.
 #   make -j8        -> deeppde_actorcritic_amd/libdpac.so
 # Each equation family's kernels are compiled once per dtype AND state dimension (one object
-# each, registered at load time: Registrar in dpac_kernels.h), so the heavy template
+# each, registered at load time: Registrar in dpac_launch.h), so the heavy template
 # instantiations build in parallel.
 HIPCC     ?= /opt/rocm/bin/hipcc
 ARCH      ?= gfx950
@@ -59,7 +59,7 @@ $(LIB): $(OBJS)
 # Dimension plugins: the equation kernels for state dimensions outside DIMS, one shared
 # object per dimension, $(PKG)/libdpac_d<D>.so, linked against libdpac.so; _lib.load() loads
 # every plugin beside libdpac.so, and its instantiations register into the same dispatch table
-# (Registrar, dpac_kernels.h).  VDP needs an even dimension (d = 2c).
+# (Registrar, dpac_launch.h).  VDP needs an even dimension (d = 2c).
 #   make ext EXT_DIMS=7,12
 EXT_DIMS  ?= 7
 EXT_LIST  := $(subst $(comma), ,$(EXT_DIMS))

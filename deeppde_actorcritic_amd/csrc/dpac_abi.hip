@@ -8,8 +8,8 @@
 #include "dpac_kernels.h"
 
 namespace dpac {
-// The instantiation table the equation TUs fill at load time (Registrar, dpac_kernels.h):
-// [equation id][dim][f64] (dim up to kMaxRegDim, dpac_kernels.h, checked at build time by
+// The instantiation table the equation TUs fill at load time (Registrar, dpac_launch.h):
+// [equation id][dim][f64] (dim up to kMaxRegDim, dpac_launch.h, checked at build time by
 // Registrar).  Zero-initialised before any constructor runs.
 static DispatchFn g_dispatch[4][kMaxRegDim + 1][2];
 void register_dispatch(int eqn, int dim, int f64, DispatchFn fn) {

@@ -21,7 +21,7 @@ extern "C" int dpac_debug_trace(void* host, int64_t bytes) {
 #endif
 
 #if DPAC_ST_TRACE && DPAC_TU_TRACE
-// Timing builds only: copy k_rollout_staged's clock table (dpac_kernels.h) of this translation
+// Timing builds only: copy k_rollout_staged's clock table (dpac_rollout_staged.h) of this translation
 // unit to the host (tools/probe_staged_trace.py).
 extern "C" int dpac_debug_staged_trace(void* host, int64_t bytes) {
   const int64_t n = bytes < (int64_t)sizeof(dpac::g_st_trace) ? bytes : (int64_t)sizeof(dpac::g_st_trace);

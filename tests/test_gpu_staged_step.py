@@ -1,5 +1,4 @@
-"""The staged rollout (k_rollout_staged, with whichever step body the library was built with:
-Transition's by default, its own under -DDPAC_ST_STEP=1) against k_rollout
+"""The staged rollout (k_rollout_staged, which has its own step body) against k_rollout
 (DPAC_ROLLOUT_STAGED=0, Transition's arithmetic): bitwise equality of every output on starts
 placed by hand so that each branch of the step runs — sampled starts may never leave the ball
 in T = 0.2.
@@ -7,7 +6,7 @@ in T = 0.2.
 Coverage: the dw-from-memory cases launch k_rollout_staged in both dtypes, the in-kernel Philox
 cases in float (all four equations here have the 2 components per lane its generator variant
 needs).  The 48 float64 Philox cases are part of the required matrix but launch k_rollout both
-times (the generator variant is float-only, run_op's kGenOk): they pin that dispatch, they do
+times (the generator variant is float-only, launch_rollout's kGenOk): they pin that dispatch, they do
 not exercise the staged step, and are not to be counted as coverage of it.
 
 Start radii (start_points): the rows cycle through 17 classes from the centre to just inside R,

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time breakdown of the staged rollout kernel from a -DDPAC_ST_TRACE=1 build (GPU only): lane 0
 of every wavefront of the first and the last workgroup of k_rollout_staged records the shader
-clock at fixed points (ST_MARK in dpac_kernels.h).  Runs bench.py's headline launch (LQR d = 20,
+clock at fixed points (ST_MARK in dpac_rollout_staged.h).  Runs bench.py's headline launch (LQR d = 20,
 B = 4096, N = 200, rotating HBM-cold buffer sets) and prints the table of the last launch.
 
     bash tools/build_variants.sh "sttrace:-DDPAC_ST_TRACE=1 -DDPAC_TU_TRACE=1"

@@ -20,7 +20,7 @@ import statistics
 
 # the last template argument is GEN: 0 = dw read from HBM (the headline); the in-kernel Philox
 # variant runs the same kernel with generator wavefronts (GEN = 12) and is not counted here
-KERNEL = "k_rollout_staged<float, dpac::EqLQR<float, 20, 16>, 20, 1, 0, 8, 0>"
+KERNEL = "k_rollout_staged<float, dpac::EqLQR<float, 20, 16>, 20, 1, 0, 0>"
 B, N, D, HBM = 4096, 200, 20, 8000.0
 
 
