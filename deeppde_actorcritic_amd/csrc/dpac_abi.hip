@@ -37,6 +37,9 @@ int critic_loss_launch(int dtype, int64_t B, const void* V, const void* y, const
 int adam_launch(int dtype, int n, const int64_t* numel, void* const* var, const void* const* grad,
                 void* const* m, void* const* v, double alpha, double b1, double b2, double eps,
                 hipStream_t s);
+int adam_step_launch(int dtype, int n, const int64_t* numel, void* const* var, const void* const* grad,
+                     void* const* m, void* const* v, dpac_adam_state* state, const void* table,
+                     int64_t table_len, double b1, double b2, double eps, int advance, hipStream_t s);
 
 namespace {
 thread_local std::string g_err;
@@ -957,6 +960,34 @@ int dpac_adam_apply(int32_t dtype, int32_t n_tensors, const int64_t* numel, void
   }
   const int r = adam_launch(dtype, n_tensors, numel, var, grad, m, v, alpha, beta_1, beta_2,
                             epsilon, (hipStream_t)stream);
+  if (r != 0) return fail(r, "kernel launch failed: %s", hipGetErrorString((hipError_t)r));
+  return ok();
+}
+
+int dpac_adam_step(int32_t dtype, int32_t n_tensors, const int64_t* numel, void* const* var,
+                   const void* const* grad, void* const* m, void* const* v, dpac_adam_state* state,
+                   const void* alpha_table, int64_t table_len, double beta_1, double beta_2,
+                   double epsilon, int32_t advance, void* stream) {
+  if (dtype != DPAC_F32 && dtype != DPAC_F64) return fail(DPAC_EINVAL, "bad dtype %d", dtype);
+  if (n_tensors < 0) return fail(DPAC_EINVAL, "n_tensors must be >= 0 (got %d)", n_tensors);
+  DPAC_REQUIRE(state);
+  DPAC_REQUIRE(alpha_table);
+  if (table_len < 1) return fail(DPAC_EINVAL, "table_len must be >= 1 (got %lld)", (long long)table_len);
+  if (n_tensors == 0 && !advance) return ok();
+  if (n_tensors > 0) {
+    DPAC_REQUIRE(numel);
+    DPAC_REQUIRE(var);
+    DPAC_REQUIRE(grad);
+    DPAC_REQUIRE(m);
+    DPAC_REQUIRE(v);
+  }
+  for (int i = 0; i < n_tensors; ++i) {
+    if (numel[i] < 1) return fail(DPAC_EINVAL, "tensor %d: numel must be >= 1", i);
+    if (!var[i] || !grad[i] || !m[i] || !v[i])
+      return fail(DPAC_EINVAL, "tensor %d: a pointer is NULL", i);
+  }
+  const int r = adam_step_launch(dtype, n_tensors, numel, var, grad, m, v, state, alpha_table, table_len,
+                                 beta_1, beta_2, epsilon, advance, (hipStream_t)stream);
   if (r != 0) return fail(r, "kernel launch failed: %s", hipGetErrorString((hipError_t)r));
   return ok();
 }

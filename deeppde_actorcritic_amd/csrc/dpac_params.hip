@@ -1,6 +1,7 @@
 // dpac_params.hip — kernels on the parameters of the MLPs rather than on
 // trajectories: the derived tensors every MLP kernel reads (dpac_mlp_prepare) and
-// the optimizer step (dpac_adam_apply); and the critic loss's gradient at V's output
+// the optimizer step (dpac_adam_apply, and dpac_adam_step with its step count and
+// alpha schedule in device memory); and the critic loss's gradient at V's output
 // (dpac_critic_loss_grad), the one elementwise step between the critic's kernels.
 //
 // Adam: one optimizer step of TF-form Adam over a list of parameter tensors in
@@ -14,6 +15,12 @@
 // as separate elementwise tensor ops.  Each workgroup row (blockIdx.y) owns one
 // tensor; blocks stride over its elements.  Elementwise and HBM-bound: 16 bytes
 // read + 12 written per fp32 element.
+//
+// dpac_adam_step is the same update with alpha read from a device table indexed
+// by a device step counter (dpac_adam_state), so a captured launch follows the
+// schedule under graph replay.  Every update launch of one call reads the counter;
+// a one-thread launch behind them on the same stream advances it, so no workgroup
+// can see a counter that an earlier one already moved.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -60,6 +67,37 @@ __global__ __launch_bounds__(kAdamThreads) void k_adam(const AdamArgs<T> a) {
   }
 }
 
+// k_adam with alpha = table[min(t, table_len) - 1], t = state->iterations + 1 (the same
+// operations in the same order; alpha is a T read from memory instead of an argument).
+template <typename T>
+__global__ __launch_bounds__(kAdamThreads) void k_adam_step(const AdamArgs<T> a,
+                                                            const dpac_adam_state* __restrict__ state,
+                                                            const T* __restrict__ table, int64_t table_len) {
+  const int i = blockIdx.y;
+  const int64_t n = a.numel[i];
+  T* __restrict__ var = a.var[i];
+  const T* __restrict__ g = a.grad[i];
+  T* __restrict__ m = a.m[i];
+  T* __restrict__ v = a.v[i];
+  const int64_t t = state->iterations + 1;
+  const T alpha = table[std::max<int64_t>(std::min(t, table_len), 1) - 1];
+  for (int64_t e = (int64_t)blockIdx.x * kAdamThreads + threadIdx.x; e < n;
+       e += (int64_t)gridDim.x * kAdamThreads) {
+    const T ge = g[e];
+    T me = m[e];
+    T ve = v[e];
+    me = me + (ge - me) * a.omb1;
+    ve = ve + (ge * ge - ve) * a.omb2;
+    const T den = sqrt(ve) + a.eps;
+    var[e] = var[e] - (me * alpha) / den;
+    m[e] = me;
+    v[e] = ve;
+  }
+}
+
+// One thread, launched behind a call's update launches: the counter moves once they are done.
+__global__ void k_adam_advance(dpac_adam_state* state) { state->iterations = state->iterations + 1; }
+
 template <typename T>
 int launch(int n, const int64_t* numel, void* const* var, const void* const* grad, void* const* m,
            void* const* v, double alpha, double b1, double b2, double eps, hipStream_t s) {
@@ -83,6 +121,38 @@ int launch(int n, const int64_t* numel, void* const* var, const void* const* gra
     hipLaunchKernelGGL(k_adam<T>, dim3(gx, (unsigned)cnt), dim3(kAdamThreads), 0, s, a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
+  }
+  return 0;
+}
+
+template <typename T>
+int launch_step(int n, const int64_t* numel, void* const* var, const void* const* grad, void* const* m,
+                void* const* v, dpac_adam_state* state, const void* table, int64_t table_len, double b1,
+                double b2, double eps, int advance, hipStream_t s) {
+  for (int base = 0; base < n; base += kAdamMax) {
+    const int cnt = std::min(kAdamMax, n - base);
+    AdamArgs<T> a{};
+    int64_t mx = 1;
+    for (int j = 0; j < cnt; ++j) {
+      a.numel[j] = numel[base + j];
+      a.var[j] = (T*)var[base + j];
+      a.grad[j] = (const T*)grad[base + j];
+      a.m[j] = (T*)m[base + j];
+      a.v[j] = (T*)v[base + j];
+      mx = std::max(mx, a.numel[j]);
+    }
+    a.omb1 = T(1) - (T)b1;
+    a.omb2 = T(1) - (T)b2;
+    a.eps = (T)eps;
+    const unsigned gx = (unsigned)std::min<int64_t>((mx + kAdamThreads - 1) / kAdamThreads, 64);
+    hipLaunchKernelGGL(k_adam_step<T>, dim3(gx, (unsigned)cnt), dim3(kAdamThreads), 0, s, a,
+                       (const dpac_adam_state*)state, (const T*)table, table_len);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+  }
+  if (advance) {
+    hipLaunchKernelGGL(k_adam_advance, dim3(1), dim3(1), 0, s, state);
+    return (int)hipGetLastError();
   }
   return 0;
 }
@@ -290,6 +360,14 @@ int adam_launch(int dtype, int n, const int64_t* numel, void* const* var, const 
                 hipStream_t s) {
   return dtype == DPAC_F64 ? launch<double>(n, numel, var, grad, m, v, alpha, b1, b2, eps, s)
                            : launch<float>(n, numel, var, grad, m, v, alpha, b1, b2, eps, s);
+}
+
+int adam_step_launch(int dtype, int n, const int64_t* numel, void* const* var, const void* const* grad,
+                     void* const* m, void* const* v, dpac_adam_state* state, const void* table,
+                     int64_t table_len, double b1, double b2, double eps, int advance, hipStream_t s) {
+  return dtype == DPAC_F64
+             ? launch_step<double>(n, numel, var, grad, m, v, state, table, table_len, b1, b2, eps, advance, s)
+             : launch_step<float>(n, numel, var, grad, m, v, state, table, table_len, b1, b2, eps, advance, s);
 }
 
 }  // namespace dpac

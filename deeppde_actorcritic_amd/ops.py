@@ -1002,3 +1002,44 @@ def adam_apply(vs, gs, ms, ss, alpha: float, beta_1: float, beta_2: float, eps: 
     n, numel, pv, pg, pm, ps = args
     call("dpac_adam_apply", _dtype_id(vs[0]), n, numel, pv, pg, pm, ps, float(alpha),
          float(beta_1), float(beta_2), float(eps), _stream(vs[0]))
+
+
+def adam_state(device) -> torch.Tensor:
+    """A zeroed dpac_adam_state (int64 [iterations, reserved]) on `device`."""
+    return torch.zeros(2, dtype=torch.int64, device=device)
+
+
+def adam_step(vs, gs, ms, ss, state, table, beta_1: float, beta_2: float, eps: float, advance=True):
+    """adam_apply with the step's alpha read on the device: alpha = table[min(t, len) - 1],
+    t = state[0] + 1 (dpac_adam_step), so the launch can be captured in a HIP graph and follows
+    the schedule under replay.  state: adam_state(); table: the 1-D device array of alphas in the
+    variables' dtype (solver.adam_alpha_table).  advance: state[0] += 1 once the whole call has
+    read it; with empty lists only that.  Pointer arrays cached as adam_apply's."""
+    _require_gpu(state, table, *vs, *gs, *ms, *ss)
+    _check_same(table, *vs, *gs, *ms, *ss)
+    if (state.dtype != torch.int64 or state.numel() < 2 or state.device != table.device
+            or not state.is_contiguous()):
+        raise ValueError("adam_step: state must be ops.adam_state() on the table's device")
+    if table.dim() != 1 or table.numel() < 1 or not table.is_contiguous():
+        raise ValueError("adam_step: table must be a contiguous 1-D tensor with at least one entry")
+    key = tuple(t.data_ptr() for t in (*vs, *gs, *ms, *ss))
+    args = _ADAM_ARGS.get(key)
+    if args is None:
+        for group in (gs, ms, ss):
+            if len(group) != len(vs):
+                raise ValueError("adam_step: one gradient and one pair of moments per parameter")
+            for v, t in zip(vs, group):
+                if t.shape != v.shape or not t.is_contiguous():
+                    raise ValueError("adam_step: gradients and moments must match the "
+                                     "parameters' shapes and be contiguous")
+        if not all(v.is_contiguous() for v in vs):
+            raise ValueError("adam_step: parameters must be contiguous")
+        n = len(vs)
+        arr = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
+        args = (n, (ctypes.c_int64 * n)(*[v.numel() for v in vs]), arr(vs), arr(gs), arr(ms), arr(ss))
+        if len(_ADAM_ARGS) > 64:
+            _ADAM_ARGS.clear()
+        _ADAM_ARGS[key] = args
+    n, numel, pv, pg, pm, ps = args
+    call("dpac_adam_step", _dtype_id(table), n, numel, pv, pg, pm, ps, state.data_ptr(), table.data_ptr(),
+         table.numel(), float(beta_1), float(beta_2), float(eps), 1 if advance else 0, _stream(table))

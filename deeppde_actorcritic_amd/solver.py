@@ -261,25 +261,94 @@ def tf_adam_scalars(lr, t, b1, b2, dtype):
     return float(alpha), float(one - b1t), float(one - b2t)
 
 
+# DPAC_ADAM=device (default): the optimizer's step count and its alpha schedule live in device
+# memory (dpac_adam_step reads alpha from a host-built table, adam_alpha_table), so the step is
+# captured inside the solver's HIP graphs and follows the schedule under replay; "host": the
+# schedule and the bias correction on the host, alpha passed by value to dpac_adam_apply, the
+# step launched between the graphs (the earlier path, and the bitwise reference of the device one).
+ADAM = os.environ.get("DPAC_ADAM", "device")
+if ADAM not in ("device", "host"):
+    raise ValueError(f"DPAC_ADAM must be 'device' or 'host', got {ADAM!r}")
+ADAM_TABLE_CAP = 1 << 22  # entries; betas whose table would be longer keep the host path
+
+_ALPHA_TABLES = {}
+
+
+def _alpha_saturated(t, b1, b2, dtype):
+    """Whether both bias corrections of step t round to exactly 1 in the variables' dtype
+    (T(1) - beta_i^t == T(1)): then alpha == T(lr), and since beta_i^t only shrinks, for every
+    later step too."""
+    f = np.float32 if dtype == torch.float32 else np.float64
+    one = f(1)
+    return bool(one - np.power(f(b1), f(t)) == one and one - np.power(f(b2), f(t)) == one)
+
+
+def adam_alpha_table(schedule, beta_1, beta_2, dtype):
+    """The alphas dpac_adam_step reads, as a numpy array in the variables' dtype: entry t-1 is
+    tf_adam_scalars(schedule(t-1), t, ...)[0], up to the first t that is past the schedule's last
+    boundary and at which alpha == T(values[-1]) for good (_alpha_saturated), so that clamping
+    the index at the table's end gives every later step's alpha exactly.  None when that takes
+    more than ADAM_TABLE_CAP entries (betas within an ulp of 1).  A pure host function."""
+    f = np.float32 if dtype == torch.float32 else np.float64
+    key = (tuple(schedule.boundaries), tuple(schedule.values), float(beta_1), float(beta_2), f)
+    if key in _ALPHA_TABLES:
+        return _ALPHA_TABLES[key]
+    first = (max(schedule.boundaries) + 2) if schedule.boundaries else 1  # schedule(t-1) is the last value
+    table = None
+    if first <= ADAM_TABLE_CAP and _alpha_saturated(ADAM_TABLE_CAP, beta_1, beta_2, dtype):
+        out, t = [], 1
+        while True:
+            out.append(tf_adam_scalars(schedule(t - 1), t, beta_1, beta_2, dtype)[0])
+            if t >= first and _alpha_saturated(t, beta_1, beta_2, dtype):
+                break
+            t += 1
+        table = np.asarray(out, dtype=f)
+        table.setflags(write=False)
+    _ALPHA_TABLES[key] = table
+    return table
+
+
 class TFAdam:
     """Adam with TensorFlow's update (ResourceApplyAdam):
         alpha = lr * sqrt(1 - b2^t) / (1 - b1^t)
         m += (g - m)(1 - b1);  v += (g^2 - v)(1 - b2);  var -= m*alpha / (sqrt(v) + eps)
     every scalar formed in the variables' dtype (tf_adam_scalars);
     lr = schedule(iterations) before the increment, t = iterations + 1.  None
-    gradients are skipped (Keras filters them), iterations still advance."""
+    gradients are skipped (Keras filters them), iterations still advance.
+
+    On the GPU with ADAM == "device" the step count also lives in device memory and alpha comes
+    from a device table (dpac_adam_step), so a step can be captured in a HIP graph (launch());
+    `iterations` stays the host's count, advanced by apply_gradients or, for a replayed step, by
+    the caller."""
 
     def __init__(self, schedule, beta_1=0.9, beta_2=0.999, epsilon=1e-8):
         self.schedule, self.b1, self.b2, self.eps = schedule, beta_1, beta_2, epsilon
         self.iterations = 0
         self.state = {}
+        self._dev = None    # ops.adam_state() once a step ran on the GPU (ADAM == "device")
+        self._snap = None   # a copy of it made by snapshot(), for a part of a step on another stream
+        self._table = None  # adam_alpha_table on that device; False: no table, host path
 
-    @torch.no_grad()
-    def apply_gradients(self, grads_and_vars, advance=True):
-        """advance=False leaves `iterations` unchanged, so one optimizer step can be
-        applied in parts (disjoint variable sets, same lr and t)."""
-        lr = self.schedule(self.iterations)
-        t = self.iterations + 1
+    def device_ready(self, like) -> bool:
+        """Make the device counter (from the host count) and the alpha table on `like`'s device
+        in its dtype, once; False when the step stays on the host path (ADAM == "host", or betas
+        without a table)."""
+        if ADAM != "device" or self._table is False:
+            return False
+        if self._table is None:
+            tab = adam_alpha_table(self.schedule, self.b1, self.b2, like.dtype)
+            if tab is None:
+                self._table = False
+                return False
+            self._table = torch.from_numpy(tab.copy()).to(like.device)
+            self._dev = ops.adam_state(like.device)
+            self._dev[0] = self.iterations
+            self._snap = self._dev.clone()
+        elif self._table.dtype != like.dtype or self._table.device != like.device:
+            raise TypeError("TFAdam: the variables changed dtype or device")
+        return True
+
+    def _gather(self, grads_and_vars):
         gs, vs, ms, ss = [], [], [], []
         for g, v in grads_and_vars:
             if g is None:
@@ -288,6 +357,45 @@ class TFAdam:
             if st is None:
                 st = self.state[v] = (torch.zeros_like(v), torch.zeros_like(v))
             gs.append(g); vs.append(v); ms.append(st[0]); ss.append(st[1])
+        return gs, vs, ms, ss
+
+    @torch.no_grad()
+    def prepare(self, grads_and_vars) -> bool:
+        """Everything launch() needs that must not be made inside a graph capture: the moments
+        of the variables with a gradient, the device counter and the table.  False: host path."""
+        gs, vs, _, _ = self._gather(grads_and_vars)
+        return bool(vs) and vs[0].is_cuda and self.device_ready(vs[0])
+
+    @torch.no_grad()
+    def snapshot(self):
+        """Copy the device counter (current stream; capturable) for launch(snap=True)."""
+        self._snap.copy_(self._dev)
+
+    @torch.no_grad()
+    def launch(self, grads_and_vars, advance=True, snap=False):
+        """One dpac_adam_step launch on the current stream, the host count untouched: the form a
+        HIP graph captures (after prepare()).  t is the device counter's; snap: that of the last
+        snapshot() instead (never advanced), for a part of a step that another stream's part,
+        unordered with this one, completes and advances."""
+        gs, vs, ms, ss = self._gather(grads_and_vars)
+        ops.adam_step([v.data for v in vs], [g.detach().contiguous() for g in gs], ms, ss,
+                      self._snap if snap else self._dev, self._table, self.b1, self.b2, self.eps,
+                      advance and not snap)
+
+    @torch.no_grad()
+    def apply_gradients(self, grads_and_vars, advance=True):
+        """advance=False leaves `iterations` unchanged, so one optimizer step can be
+        applied in parts (disjoint variable sets, same lr and t)."""
+        lr = self.schedule(self.iterations)
+        t = self.iterations + 1
+        gs, vs, ms, ss = self._gather(grads_and_vars)
+        if gs and gs[0].is_cuda and self.device_ready(vs[0]):  # alpha and t read on the device
+            self.launch(zip(gs, vs), advance)
+            if advance:
+                self.iterations += 1
+            return
+        if not gs and advance and self._dev is not None:  # no gradient at all: the step still counts
+            ops.adam_step([], [], [], [], self._dev, self._table, self.b1, self.b2, self.eps, True)
         if gs:
             alpha, omb1, omb2 = tf_adam_scalars(lr, t, self.b1, self.b2, vs[0].dtype)
         if gs and gs[0].is_cuda:  # one dpac_adam_apply launch (same arithmetic, same order)
@@ -302,8 +410,43 @@ class TFAdam:
         if advance:
             self.iterations += 1
 
-    def state_dict(self):
-        return {"iterations": self.iterations}
+    def device_iterations(self):
+        """The device counter (synchronises), or None while no step has run on the device path."""
+        if self._dev is None:
+            return None
+        return int(self._dev[0].item())
+
+    def state_dict(self, variables=None):
+        """`iterations` and, per variable in order (`variables`, default: in the order the
+        optimizer first saw them), the moments m and v on the CPU (None: no moments yet)."""
+        vs = list(self.state) if variables is None else list(variables)
+        c = lambda t: t.detach().to("cpu").clone()
+        sts = [self.state.get(v) for v in vs]
+        return {"iterations": self.iterations,
+                "m": [None if st is None else c(st[0]) for st in sts],
+                "v": [None if st is None else c(st[1]) for st in sts]}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd, variables=None):
+        """Restore state_dict(): the host count, the device counter and the moments, written in
+        place where they exist (captured graphs hold their addresses)."""
+        vs = list(self.state) if variables is None else list(variables)
+        ms, ss = sd.get("m", []), sd.get("v", [])
+        if len(ms) != len(vs) or len(ss) != len(vs):
+            raise ValueError(f"TFAdam.load_state_dict: moments for {len(ms)} variables, have {len(vs)}")
+        for v, m, s in zip(vs, ms, ss):
+            st = self.state.get(v)
+            if m is None:
+                if st is not None:
+                    st[0].zero_(); st[1].zero_()
+                continue
+            if st is None:
+                st = self.state[v] = (torch.zeros_like(v), torch.zeros_like(v))
+            st[0].copy_(torch.as_tensor(m).to(st[0]))
+            st[1].copy_(torch.as_tensor(s).to(st[1]))
+        self.iterations = int(sd["iterations"])
+        if self._dev is not None:
+            self._dev[0] = self.iterations
 
 
 # HIP-graph captures are thread-local: with a torch.distributed "nccl" (RCCL) process group
@@ -313,26 +456,47 @@ class TFAdam:
 _CAPTURE_MODE = "thread_local"
 
 
-class _GradGraph:
-    """One gradient evaluation (forward + backward, no optimizer step) captured as a
-    HIP graph over static input buffers.  Replaying it after copying a fresh batch
-    in replaces the ~10^3 kernel launches of a step (the actor's reverse time loop,
-    the critic's G network and TD assembly) with one graph launch; the optimizer
-    still runs eagerly on the returned gradients, whose buffers the next replay
-    overwrites.  Parameters are updated in place, so every replay sees the
-    current weights."""
+class _GraphStep:
+    """An optimizer step (or one part of it) that a graph appends to its gradients in the
+    capture only: the graph constructors' warm-up runs apply no step.  prepare(grads), outside the
+    capture, makes what the launch needs and tells whether the optimizer's step can be captured
+    (TFAdam.prepare); calling it with the captured gradient buffers launches dpac_adam_step."""
 
-    def __init__(self, fn, batch: TrajectoryBatch):
+    def __init__(self, opt, variables, advance=True, snap=False):
+        """snap: the step reads the counter's snapshot (TFAdam.launch) and leaves the counter."""
+        self.opt, self.variables, self.advance, self.snap = opt, list(variables), advance, snap
+
+    def prepare(self, grads) -> bool:
+        return self.opt.prepare(zip(grads, self.variables))
+
+    def __call__(self, grads):
+        self.opt.launch(zip(grads, self.variables), self.advance, self.snap)
+
+
+class _GradGraph:
+    """One gradient evaluation (forward + backward) captured as a HIP graph over static
+    input buffers, with the optimizer step on those gradients at its end when `step` (a
+    _GraphStep) is given and can be captured (`stepped`); otherwise the optimizer runs
+    eagerly on the returned gradients, whose buffers the next replay overwrites.
+    Replaying it after copying a fresh batch in replaces the ~10^3 kernel launches of a
+    step (the actor's reverse time loop, the critic's G network and TD assembly) with one
+    graph launch.  Parameters are updated in place, so every replay sees the current
+    weights."""
+
+    def __init__(self, fn, batch: TrajectoryBatch, step=None):
         self.static = TrajectoryBatch(*[t.clone() for t in batch])
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):  # warm-up outside the capture (allocator, autograd)
             for _ in range(2):
-                fn(self.static)
+                out = fn(self.static)
         torch.cuda.current_stream().wait_stream(side)
+        self.stepped = step is not None and step.prepare(out)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph, capture_error_mode=_CAPTURE_MODE):
             self.out = fn(self.static)
+            if self.stepped:
+                step(self.out)
 
     def __call__(self, batch: TrajectoryBatch):
         for dst, src in zip(self.static, batch):
@@ -360,9 +524,10 @@ class _SplitActorGraphs:
     the actor's parameters, which the critic step does not change) and the gradient
     from those saves (after the critic update, which the terminal value V(x_N) needs;
     solver.py:67-70 order).  The backward graph reads the forward graph's outputs in
-    place: nothing is copied between them."""
+    place: nothing is copied between them.  With `step` (a _GraphStep that can be captured:
+    `stepped`) the actor's optimizer step ends the backward graph, behind its guard fallbacks."""
 
-    def __init__(self, fwd_fn, bwd_fn, batch: TrajectoryBatch, side, defer=None):
+    def __init__(self, fwd_fn, bwd_fn, batch: TrajectoryBatch, side, defer=None, step=None):
         """defer: a context manager factory yielding the list the backward's deferred guard
         fallbacks go to (ActorCriticSolver._deferring); they become the graph g_redo."""
         self.static = TrajectoryBatch(*[t.clone() for t in batch])
@@ -372,10 +537,11 @@ class _SplitActorGraphs:
         with torch.cuda.stream(side):  # warm-up outside the capture (allocator, autograd)
             for _ in range(2):
                 with defer() as fns:
-                    bwd_fn(fwd_fn(self.static))
+                    out = bwd_fn(fwd_fn(self.static))
                 for f in fns:
                     f()
         torch.cuda.current_stream().wait_stream(side)
+        self.stepped = step is not None and step.prepare(out)
         self.g_fwd, self.g_bwd = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.g_fwd, capture_error_mode=_CAPTURE_MODE):
             self.fwd = fwd_fn(self.static)
@@ -385,7 +551,11 @@ class _SplitActorGraphs:
             if not GUARD_DEFER_JOIN:  # the fallbacks at the chain's end, in the same graph
                 for f in self.redo_fns:
                     f()
-        self.g_redo = _capture_redo(self.redo_fns) if GUARD_DEFER_JOIN else None
+                if self.stepped:
+                    step(self.out)
+        # DPAC_GUARD_DEFER=join: the step reads the gradients behind the joined fallbacks
+        tail = [lambda: step(self.out)] if self.stepped else []
+        self.g_redo = _capture_redo(list(self.redo_fns) + tail) if GUARD_DEFER_JOIN else None
 
     def launch_forward(self, batch: TrajectoryBatch):
         """On the side stream, after the work queued so far on the current stream."""
@@ -403,8 +573,8 @@ class _SplitActorGraphs:
         return list(self.out)
 
     def redo(self):
-        """The backward's deferred guard fallbacks, on the current stream (DPAC_GUARD_DEFER=join;
-        otherwise they ended the backward graph)."""
+        """The backward's deferred guard fallbacks (and then the captured step), on the current
+        stream (DPAC_GUARD_DEFER=join; otherwise they ended the backward graph)."""
         if self.g_redo is not None:
             self.g_redo.replay()
 
@@ -417,9 +587,17 @@ class _SplitCriticGraphs:
     only the head's outputs, so it is launched on a side stream as soon as the head is done:
     it runs beside V's backward, V's Adam step and the actor's terminal V(x_N) (a chain of
     small kernels that leaves most CUs idle) and then beside the actor's BPTT, which needs
-    the updated V only (solver.py:221), not G."""
+    the updated V only (solver.py:221), not G.
 
-    def __init__(self, head_fn, v_fn, back_fn, batch: TrajectoryBatch, side, defer=None):
+    With v_step and g_step (_GraphSteps that can be captured: `stepped`) the critic's optimizer
+    step is captured in its two parts: V's ends V's backward graph and G's, which advances the
+    step counter, ends G's backward graph on the side stream.  The two are not ordered with each
+    other (DPAC_GBACK=early launches the G backward before V's step), so V's part reads t from a
+    snapshot of the counter that the head graph takes before either can run: the advance cannot
+    reach what V's part reads."""
+
+    def __init__(self, head_fn, v_fn, back_fn, batch: TrajectoryBatch, side, defer=None,
+                 v_step=None, g_step=None):
         """defer: as _SplitActorGraphs's, for the G backward (graph g_redo)."""
         self.static = TrajectoryBatch(*[t.clone() for t in batch])
         self.side = side
@@ -428,24 +606,34 @@ class _SplitCriticGraphs:
         with torch.cuda.stream(side):  # warm-up outside the capture (allocator, autograd)
             for _ in range(2):
                 h = head_fn(self.static)
-                v_fn(h[0])
+                gv = v_fn(h[0])
                 with defer() as fns:
-                    back_fn((None,) + tuple(h[1]))
+                    gb = back_fn((None,) + tuple(h[1]))
                 for f in fns:
                     f()
         torch.cuda.current_stream().wait_stream(side)
+        self.stepped = (v_step is not None and g_step is not None and v_step.prepare(gv)
+                        and g_step.prepare(gb))
         self.g_head, self.g_v, self.g_back = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.g_head, capture_error_mode=_CAPTURE_MODE):
+            if self.stepped:  # this step's t for V's part, before G's part can advance the counter
+                v_step.opt.snapshot()
             self.head_out = head_fn(self.static)
         with torch.cuda.graph(self.g_v, capture_error_mode=_CAPTURE_MODE):
             self.v_out = v_fn(self.head_out[0])
+            if self.stepped:
+                v_step(self.v_out)
         with torch.cuda.graph(self.g_back, capture_error_mode=_CAPTURE_MODE):
             with defer() as self.redo_fns:
                 self.back_out = back_fn((None,) + tuple(self.head_out[1]))
             if not GUARD_DEFER_JOIN:  # the fallbacks at the chain's end, on the side stream
                 for f in self.redo_fns:
                     f()
-        self.g_redo = _capture_redo(self.redo_fns) if GUARD_DEFER_JOIN else None
+                if self.stepped:
+                    g_step(self.back_out)
+        # DPAC_GUARD_DEFER=join: G's step behind the joined fallbacks, on the current stream
+        tail = [lambda: g_step(self.back_out)] if self.stepped else []
+        self.g_redo = _capture_redo(list(self.redo_fns) + tail) if GUARD_DEFER_JOIN else None
 
     def head(self, batch: TrajectoryBatch):
         """The head graph on the current stream."""
@@ -455,21 +643,23 @@ class _SplitCriticGraphs:
         self.g_head.replay()
 
     def grads_v(self):
-        """V's parameter gradients (current stream, after head())."""
+        """V's parameter gradients, and then V's captured step (current stream, after head())."""
         self.g_v.replay()
         return list(self.v_out)
 
     def launch_back(self, after: torch.cuda.Event):
-        """G's parameter gradients, replayed on the side stream once `after` (recorded
-        behind head()) has passed; use them on the side stream (valid once redo() has run)."""
+        """G's parameter gradients (and then G's captured step), replayed on the side stream once
+        `after` (recorded behind head()) has passed; use them on the side stream (valid once
+        redo() has run)."""
         self.side.wait_event(after)
         with torch.cuda.stream(self.side):
             self.g_back.replay()
         return list(self.back_out)
 
     def redo(self):
-        """The G backward's deferred guard fallbacks, on the current stream after it has waited
-        for the side stream (DPAC_GUARD_DEFER=join; otherwise they ended the backward graph)."""
+        """The G backward's deferred guard fallbacks (and then G's captured step), on the current
+        stream after it has waited for the side stream (DPAC_GUARD_DEFER=join; otherwise they
+        ended the backward graph)."""
         if self.g_redo is not None:
             self.g_redo.replay()
 
@@ -729,20 +919,32 @@ class ActorCriticSolver(object):
     def _global(self, data, total):
         return data.x0.shape[0], total
 
-    def _grads(self, kind, fn, data):
-        """fn(batch) -> gradients, through a captured HIP graph when enabled."""
+    def _capture_steps(self):
+        """Whether the optimizer steps go inside the graphs: the schedule on the device and no
+        process group (with one, also one of a single rank, the all-reduce sits between the
+        gradients and the step)."""
+        return self.hip_graphs and isinstance(self.par, SingleProcess) and ADAM == "device"
+
+    def _grads(self, kind, fn, data, opt=None, variables=None):
+        """fn(batch) -> (gradients, whether the graph applied opt's step on them), through a
+        captured HIP graph when enabled."""
         data = Equation.to_native(data, self.dtype)
         if not self.hip_graphs:
-            return fn(data)
+            return fn(data), False
         key = (kind, tuple(data.dw.shape))
         graph = self._graphs.get(key)
         if graph is None:
-            graph = self._graphs[key] = _GradGraph(fn, data)
-        return graph(data)
+            step = _GraphStep(opt, variables) if opt is not None and self._capture_steps() else None
+            graph = self._graphs[key] = _GradGraph(fn, data, step)
+        return graph(data), graph.stepped
 
     def train_step_critic(self, train_data, total=None):
-        g = self._grads("critic", lambda d: self.grad_critic(
-            d, training=False, cheat_control=self.cheat_control_in_critic), train_data)
+        g, stepped = self._grads("critic", lambda d: self.grad_critic(
+            d, training=False, cheat_control=self.cheat_control_in_critic), train_data,
+            self.optimizer_critic, self.critic_variables())
+        if stepped:  # applied by the replay; the host only counts it
+            self.optimizer_critic.iterations += 1
+            return
         cnt = train_data[0].shape[0]
         g = self.par.allreduce_grads(g, cnt, total or cnt * self.par.world)
         self.optimizer_critic.apply_gradients(zip(g, self.critic_variables()))
@@ -887,7 +1089,14 @@ class ActorCriticSolver(object):
         actor's BPTT (which reads V, not G).  Two gradient all-reduces per iteration (SURVEY
         §8(e)): V's half of the critic step (the actor's terminal V(x_N) needs the updated V,
         solver.py:221), then the actor's gradients and G's half in one flattened exchange (G
-        is next read by the following iteration's critic step)."""
+        is next read by the following iteration's critic step).
+
+        Without a process group and with ADAM == "device" the three optimizer launches are inside the graphs
+        (V's at the end of V's backward graph, the actor's at the end of its backward graph, G's
+        at the end of G's backward graph on its side stream): once the graphs exist the host launches no
+        optimizer kernel and only counts the steps.  The streams that next read a network are
+        behind its step: this stream runs V's and the actor's and waits for the G side stream
+        before the iteration ends, and the next forward rollout's side stream waits for this one."""
         if not self._actor_split_ok():
             self.train_step_critic(data_critic, total)
             self.train_step_actor(data_actor, total)
@@ -895,12 +1104,15 @@ class ActorCriticSolver(object):
         da = Equation.to_native(data_actor, self.dtype)
         if self._side is None:
             self._side = torch.cuda.Stream()
+        cap = self._capture_steps()
+        oa, oc = self.optimizer_actor, self.optimizer_critic
+        astep = lambda: _GraphStep(oa, self.actor_variables()) if cap else None
         if not self._critic_split_ok():
             key = ("actor_split", tuple(da.dw.shape))
             sg = self._graphs.get(key)
             if sg is None:
                 sg = self._graphs[key] = _SplitActorGraphs(self.actor_forward, self.actor_grads_from,
-                                                           da, self._side, self._defer())
+                                                           da, self._side, self._defer(), astep())
             sg.launch_forward(da)
             self.train_step_critic(data_critic, total)
             cg = None
@@ -912,10 +1124,14 @@ class ActorCriticSolver(object):
             sets = self._gsets.setdefault(spec, [None, None])
             p = self._parity
             if sets[p] is None:
+                mc = self.model_critic
                 sets[p] = (_SplitActorGraphs(self.actor_forward, self.actor_grads_from, da, self._side,
-                                             self._defer()),
-                           _SplitCriticGraphs(self.critic_head, self.critic_grads_v, self.critic_G_back, dc,
-                                              self._side_g, self._defer()))
+                                             self._defer(), astep()),
+                           _SplitCriticGraphs(
+                               self.critic_head, self.critic_grads_v, self.critic_G_back, dc,
+                               self._side_g, self._defer(),
+                               _GraphStep(oc, mc.NN_value.trainable_variables(), snap=True) if cap else None,
+                               _GraphStep(oc, mc.NN_value_grad.trainable_variables()) if cap else None))
             sg, cg = sets[p]
             sg.launch_forward(da)
             ccnt = dc.x0.shape[0]
@@ -925,38 +1141,83 @@ class ActorCriticSolver(object):
             head_done.record()
             if GBACK == "early":  # G's backward beside V's update and the actor's terminal V
                 gG = cg.launch_back(head_done)
-            gV = self.par.allreduce_grads(cg.grads_v(), ccnt, ctot)
+            gV = cg.grads_v()
             # one Adam step of the critic in two parts: V now (the actor reads it), G after the
             # actor's exchange (same lr and t: advance=False here)
-            self.optimizer_critic.apply_gradients(
-                zip(gV, self.model_critic.NN_value.trainable_variables()), advance=False)
+            if not cg.stepped:  # (captured: V's part ended the graph)
+                gV = self.par.allreduce_grads(gV, ccnt, ctot)
+                oc.apply_gradients(zip(gV, self.model_critic.NN_value.trainable_variables()), advance=False)
         g = sg.grads()  # the actor's terminal V(x_N), BPTT and parameter gradients
         cnt = da.x0.shape[0]
         atot = total or cnt * self.par.world
         if cg is None:
             sg.redo()
+            if sg.stepped:
+                oa.iterations += 1
+                return
             g = self.par.allreduce_grads(g, cnt, atot)
-            self.optimizer_actor.apply_gradients(zip(g, self.actor_variables()))
+            oa.apply_gradients(zip(g, self.actor_variables()))
             return
         if GBACK != "early":
             gG = cg.launch_back(head_done)
-        torch.cuda.current_stream().wait_stream(cg.side)  # G's gradients, made on the side stream
+        torch.cuda.current_stream().wait_stream(cg.side)  # G's gradients (and step), made on the side stream
         sg.redo()  # DPAC_GUARD_DEFER=join: both chains' range-guard fallbacks (no-ops unless a split
         cg.redo()  # operand overflowed); by default each chain's graph ends with its own
-        g, gG = self.par.allreduce_grads_multi([(g, cnt, atot), (gG, ccnt, ctot)])
-        self.optimizer_actor.apply_gradients(zip(g, self.actor_variables()))
-        self.optimizer_critic.apply_gradients(zip(gG, self.model_critic.NN_value_grad.trainable_variables()))
+        if not (sg.stepped and cg.stepped):
+            g, gG = self.par.allreduce_grads_multi([(g, cnt, atot), (gG, ccnt, ctot)])
+        if sg.stepped:
+            oa.iterations += 1
+        else:
+            oa.apply_gradients(zip(g, self.actor_variables()))
+        if cg.stepped:
+            oc.iterations += 1
+        else:
+            oc.apply_gradients(zip(gG, self.model_critic.NN_value_grad.trainable_variables()))
         done = torch.cuda.Event()  # every reader of this set's static inputs is behind this point
         done.record()
         self._set_done[self._parity] = done
         self._parity = (self._parity + 1) % graph_sets(ccnt)
 
     def train_step_actor(self, train_data, total=None):
-        g = self._grads("actor", lambda d: self.grad_actor(
-            d, training=False, cheat_value=self.cheat_value_in_actor, cheat_control=False), train_data)
+        g, stepped = self._grads("actor", lambda d: self.grad_actor(
+            d, training=False, cheat_value=self.cheat_value_in_actor, cheat_control=False), train_data,
+            self.optimizer_actor, self.actor_variables())
+        if stepped:  # applied by the replay; the host only counts it
+            self.optimizer_actor.iterations += 1
+            return
         cnt = train_data[0].shape[0]
         g = self.par.allreduce_grads(g, cnt, total or cnt * self.par.world)
         self.optimizer_actor.apply_gradients(zip(g, self.actor_variables()))
+
+    # ---- save and restore ----------------------------------------------------
+    def _nets(self):
+        mc = self.model_critic
+        return {"critic": mc.NN_value, "critic_grad": mc.NN_value_grad, "actor": self.model_actor.NN_control}
+
+    def state_dict(self):
+        """What a solver built from the same config needs to continue bit for bit: the three
+        networks (DeepNN.export_params), both optimizers (count and moments), the seed and the
+        sampler's call count as of the last batch consumed (a pair drawn ahead by
+        prefetch_samples is not counted: the resumed solver draws it again under the same keys)."""
+        torch.cuda.synchronize(self.device)
+        ahead = 2 if self._next_samples is not None else 0
+        return {"params": {k: n.export_params() for k, n in self._nets().items()},
+                "optimizer_critic": self.optimizer_critic.state_dict(self.critic_variables()),
+                "optimizer_actor": self.optimizer_actor.state_dict(self.actor_variables()),
+                "seed": self.seed, "sampler_calls": self._calls - ahead}
+
+    def load_state_dict(self, sd):
+        """Restore state_dict(), writing parameters and moments in place (captured graphs hold
+        their addresses); a pair drawn ahead is dropped."""
+        torch.cuda.synchronize(self.device)
+        for k, n in self._nets().items():
+            n.load_params(sd["params"][k])
+        self.optimizer_critic.load_state_dict(sd["optimizer_critic"], self.critic_variables())
+        self.optimizer_actor.load_state_dict(sd["optimizer_actor"], self.actor_variables())
+        self.seed = int(sd["seed"])
+        self._calls = int(sd["sampler_calls"])
+        self._next_samples = None
+        torch.cuda.synchronize(self.device)
 
     # ---- metrics (solver.py:109-136), reduced over ranks ---------------------
     def _mean(self, local_mean, cnt, total):

@@ -58,7 +58,7 @@ extern "C" {
  * (dpac_mlp_rows_mask_bytes, dpac_mlp_rows_{fwd,bwd}[_td1]_masked).  8: dpac_mlp gains
  * `guard_phase` (the range guard's fallback launched apart from its split-fp16 launch, below).
  * Bindings must refuse a library of another version. */
-#define DPAC_ABI_VERSION 8
+#define DPAC_ABI_VERSION 9
 
 /* status codes besides hipError_t values */
 #define DPAC_OK 0
@@ -512,6 +512,28 @@ int dpac_mlp_prepare(int32_t dtype, const dpac_mlp* net, double gamma_scale, voi
 int dpac_adam_apply(int32_t dtype, int32_t n_tensors, const int64_t* numel, void* const* var,
                     const void* const* grad, void* const* m, void* const* v, double alpha,
                     double beta_1, double beta_2, double epsilon, void* stream);
+
+/* ---- optimizer step with its schedule on the device ---------------------
+ * dpac_adam_apply's update, element for element (the same operations, order and rounding),
+ * with alpha read on the device:
+ *   t = state->iterations + 1,  alpha = alpha_table[min(t, table_len) - 1].
+ * `state` and `alpha_table` (table_len values of `dtype`, entry t-1 = the caller's alpha of
+ * step t) are device memory, so a launch captured in a HIP graph follows the schedule when it
+ * is replayed; a table that reaches the step from which alpha no longer changes covers every t.
+ * Every element of every tensor of one call sees the same t, however many launches the call
+ * takes.  advance != 0: state->iterations += 1 once the whole call has read it (a one-thread
+ * launch behind the update launches on `stream`); advance == 0 leaves it, so one optimizer step
+ * can be applied in parts (disjoint tensors, the last part advancing).  n_tensors == 0 with
+ * advance != 0 only counts the step.  The caller orders other streams' calls on the same state. */
+typedef struct dpac_adam_state { /* DEVICE memory, caller-owned */
+  int64_t iterations;            /* optimizer steps applied so far (Keras `iterations`) */
+  int64_t reserved;              /* 0 */
+} dpac_adam_state;
+
+int dpac_adam_step(int32_t dtype, int32_t n_tensors, const int64_t* numel, void* const* var,
+                   const void* const* grad, void* const* m, void* const* v,
+                   dpac_adam_state* state, const void* alpha_table, int64_t table_len,
+                   double beta_1, double beta_2, double epsilon, int32_t advance, void* stream);
 
 /* ---- the critic loss's gradient at V's outputs (one launch) -------------
  * loss_critic (solver.py:73-78) differentiated at V = NN_value([x_0; x_N; x_bdry]) (3B):
