@@ -29,7 +29,11 @@ from torch import nn
 from . import _lib, ops
 from .config import set_floatx, torch_dtype
 from .equation import SAMPLE_TYPES, SCHEMES, Equation, TrajectoryBatch, is_ekn
+from .optim import (ADAM_TABLE_CAP, PiecewiseConstantDecay, TFAdam, _alpha_saturated,  # noqa: F401
+                    adam_alpha_table, tf_adam_scalars)
 from .parallel import SingleProcess
+from .step_graphs import (_CAPTURE_MODE, _GradGraph, _GraphStep, _SplitActorGraphs,  # noqa: F401
+                          _SplitCriticGraphs)
 
 DELTA_CLIP = 50.0  # solver.py:5
 BN_EPS = 1e-6      # solver.py:242
@@ -164,7 +168,6 @@ class CriticModel(nn.Module):
         self.bsde = bsde
         self.NN_value = DeepNN(config, "critic", generator, dtype, device)
         self.NN_value_grad = DeepNN(config, "critic_grad", generator, dtype, device)
-        self.gamma = config.eqn_config.discount
         self.scheme = self.train_config.scheme
         self.td = _lib.TD1 if self.train_config.TD_type == "TD1" else _lib.TD2
 
@@ -199,7 +202,6 @@ class ActorModel(nn.Module):
             config.eqn_config, config.net_config, config.train_config)
         self.bsde = bsde
         self.NN_control = DeepNN(config, "actor", generator, dtype, device)
-        self.gamma = config.eqn_config.discount
         self.scheme = SCHEMES[self.train_config.scheme]
 
     def forward(self, inputs, model_critic, training, cheat_value, cheat_control):
@@ -234,33 +236,9 @@ class ActorModel(nn.Module):
 
 
 # ---------------------------------------------------------------------------
-# Optimizer (tf.keras Adam + PiecewiseConstantDecay, solver.py:16-21)
+# The DPAC_* knobs: read here and nowhere else (optim and step_graphs get what they decide as
+# arguments), when a solver builds an optimizer or a graph set, so a test can patch them here
 # ---------------------------------------------------------------------------
-class PiecewiseConstantDecay:
-    def __init__(self, boundaries, values):
-        if len(values) != len(boundaries) + 1:
-            raise ValueError("values must have one more entry than boundaries")
-        self.boundaries, self.values = list(boundaries), list(values)
-
-    def __call__(self, step):
-        for b, v in zip(self.boundaries, self.values):
-            if step <= b:
-                return v
-        return self.values[-1]
-
-
-def tf_adam_scalars(lr, t, b1, b2, dtype):
-    """ResourceApplyAdam's scalars in the variables' dtype T, as TF forms them (Keras
-    Adam casts lr, beta_1, beta_2 to T, beta_i_power = pow(beta_i, t) in T; the op computes
-    alpha = lr * sqrt(T(1) - beta2_power) / (T(1) - beta1_power) and T(1) - beta_i in T):
-    (alpha, 1 - b1, 1 - b2) as Python floats holding T values."""
-    f = np.float32 if dtype == torch.float32 else np.float64
-    one, b1t, b2t = f(1), f(b1), f(b2)
-    b1p, b2p = np.power(b1t, f(t)), np.power(b2t, f(t))
-    alpha = f(lr) * np.sqrt(one - b2p) / (one - b1p)
-    return float(alpha), float(one - b1t), float(one - b2t)
-
-
 # DPAC_ADAM=device (default): the optimizer's step count and its alpha schedule live in device
 # memory (dpac_adam_step reads alpha from a host-built table, adam_alpha_table), so the step is
 # captured inside the solver's HIP graphs and follows the schedule under replay; "host": the
@@ -269,400 +247,6 @@ def tf_adam_scalars(lr, t, b1, b2, dtype):
 ADAM = os.environ.get("DPAC_ADAM", "device")
 if ADAM not in ("device", "host"):
     raise ValueError(f"DPAC_ADAM must be 'device' or 'host', got {ADAM!r}")
-ADAM_TABLE_CAP = 1 << 22  # entries; betas whose table would be longer keep the host path
-
-_ALPHA_TABLES = {}
-
-
-def _alpha_saturated(t, b1, b2, dtype):
-    """Whether both bias corrections of step t round to exactly 1 in the variables' dtype
-    (T(1) - beta_i^t == T(1)): then alpha == T(lr), and since beta_i^t only shrinks, for every
-    later step too."""
-    f = np.float32 if dtype == torch.float32 else np.float64
-    one = f(1)
-    return bool(one - np.power(f(b1), f(t)) == one and one - np.power(f(b2), f(t)) == one)
-
-
-def adam_alpha_table(schedule, beta_1, beta_2, dtype):
-    """The alphas dpac_adam_step reads, as a numpy array in the variables' dtype: entry t-1 is
-    tf_adam_scalars(schedule(t-1), t, ...)[0], up to the first t that is past the schedule's last
-    boundary and at which alpha == T(values[-1]) for good (_alpha_saturated), so that clamping
-    the index at the table's end gives every later step's alpha exactly.  None when that takes
-    more than ADAM_TABLE_CAP entries (betas within an ulp of 1).  A pure host function."""
-    f = np.float32 if dtype == torch.float32 else np.float64
-    key = (tuple(schedule.boundaries), tuple(schedule.values), float(beta_1), float(beta_2), f)
-    if key in _ALPHA_TABLES:
-        return _ALPHA_TABLES[key]
-    first = (max(schedule.boundaries) + 2) if schedule.boundaries else 1  # schedule(t-1) is the last value
-    table = None
-    if first <= ADAM_TABLE_CAP and _alpha_saturated(ADAM_TABLE_CAP, beta_1, beta_2, dtype):
-        out, t = [], 1
-        while True:
-            out.append(tf_adam_scalars(schedule(t - 1), t, beta_1, beta_2, dtype)[0])
-            if t >= first and _alpha_saturated(t, beta_1, beta_2, dtype):
-                break
-            t += 1
-        table = np.asarray(out, dtype=f)
-        table.setflags(write=False)
-    _ALPHA_TABLES[key] = table
-    return table
-
-
-class TFAdam:
-    """Adam with TensorFlow's update (ResourceApplyAdam):
-        alpha = lr * sqrt(1 - b2^t) / (1 - b1^t)
-        m += (g - m)(1 - b1);  v += (g^2 - v)(1 - b2);  var -= m*alpha / (sqrt(v) + eps)
-    every scalar formed in the variables' dtype (tf_adam_scalars);
-    lr = schedule(iterations) before the increment, t = iterations + 1.  None
-    gradients are skipped (Keras filters them), iterations still advance.
-
-    On the GPU with ADAM == "device" the step count also lives in device memory and alpha comes
-    from a device table (dpac_adam_step), so a step can be captured in a HIP graph (launch());
-    `iterations` stays the host's count, advanced by apply_gradients or, for a replayed step, by
-    the caller."""
-
-    def __init__(self, schedule, beta_1=0.9, beta_2=0.999, epsilon=1e-8):
-        self.schedule, self.b1, self.b2, self.eps = schedule, beta_1, beta_2, epsilon
-        self.iterations = 0
-        self.state = {}
-        self._dev = None    # ops.adam_state() once a step ran on the GPU (ADAM == "device")
-        self._snap = None   # a copy of it made by snapshot(), for a part of a step on another stream
-        self._table = None  # adam_alpha_table on that device; False: no table, host path
-
-    def device_ready(self, like) -> bool:
-        """Make the device counter (from the host count) and the alpha table on `like`'s device
-        in its dtype, once; False when the step stays on the host path (ADAM == "host", or betas
-        without a table)."""
-        if ADAM != "device" or self._table is False:
-            return False
-        if self._table is None:
-            tab = adam_alpha_table(self.schedule, self.b1, self.b2, like.dtype)
-            if tab is None:
-                self._table = False
-                return False
-            self._table = torch.from_numpy(tab.copy()).to(like.device)
-            self._dev = ops.adam_state(like.device)
-            self._dev[0] = self.iterations
-            self._snap = self._dev.clone()
-        elif self._table.dtype != like.dtype or self._table.device != like.device:
-            raise TypeError("TFAdam: the variables changed dtype or device")
-        return True
-
-    def _gather(self, grads_and_vars):
-        gs, vs, ms, ss = [], [], [], []
-        for g, v in grads_and_vars:
-            if g is None:
-                continue
-            st = self.state.get(v)
-            if st is None:
-                st = self.state[v] = (torch.zeros_like(v), torch.zeros_like(v))
-            gs.append(g); vs.append(v); ms.append(st[0]); ss.append(st[1])
-        return gs, vs, ms, ss
-
-    @torch.no_grad()
-    def prepare(self, grads_and_vars) -> bool:
-        """Everything launch() needs that must not be made inside a graph capture: the moments
-        of the variables with a gradient, the device counter and the table.  False: host path."""
-        gs, vs, _, _ = self._gather(grads_and_vars)
-        return bool(vs) and vs[0].is_cuda and self.device_ready(vs[0])
-
-    @torch.no_grad()
-    def snapshot(self):
-        """Copy the device counter (current stream; capturable) for launch(snap=True)."""
-        self._snap.copy_(self._dev)
-
-    @torch.no_grad()
-    def launch(self, grads_and_vars, advance=True, snap=False):
-        """One dpac_adam_step launch on the current stream, the host count untouched: the form a
-        HIP graph captures (after prepare()).  t is the device counter's; snap: that of the last
-        snapshot() instead (never advanced), for a part of a step that another stream's part,
-        unordered with this one, completes and advances."""
-        gs, vs, ms, ss = self._gather(grads_and_vars)
-        ops.adam_step([v.data for v in vs], [g.detach().contiguous() for g in gs], ms, ss,
-                      self._snap if snap else self._dev, self._table, self.b1, self.b2, self.eps,
-                      advance and not snap)
-
-    @torch.no_grad()
-    def apply_gradients(self, grads_and_vars, advance=True):
-        """advance=False leaves `iterations` unchanged, so one optimizer step can be
-        applied in parts (disjoint variable sets, same lr and t)."""
-        lr = self.schedule(self.iterations)
-        t = self.iterations + 1
-        gs, vs, ms, ss = self._gather(grads_and_vars)
-        if gs and gs[0].is_cuda and self.device_ready(vs[0]):  # alpha and t read on the device
-            self.launch(zip(gs, vs), advance)
-            if advance:
-                self.iterations += 1
-            return
-        if not gs and advance and self._dev is not None:  # no gradient at all: the step still counts
-            ops.adam_step([], [], [], [], self._dev, self._table, self.b1, self.b2, self.eps, True)
-        if gs:
-            alpha, omb1, omb2 = tf_adam_scalars(lr, t, self.b1, self.b2, vs[0].dtype)
-        if gs and gs[0].is_cuda:  # one dpac_adam_apply launch (same arithmetic, same order)
-            ops.adam_apply([v.data for v in vs], [g.detach().contiguous() for g in gs], ms, ss, alpha,
-                           self.b1, self.b2, self.eps)
-        elif gs:
-            torch._foreach_add_(ms, torch._foreach_mul(torch._foreach_sub(gs, ms), omb1))
-            g2 = torch._foreach_mul(gs, gs)
-            torch._foreach_add_(ss, torch._foreach_mul(torch._foreach_sub(g2, ss), omb2))
-            den = torch._foreach_add(torch._foreach_sqrt(ss), self.eps)
-            torch._foreach_sub_(vs, torch._foreach_div(torch._foreach_mul(ms, alpha), den))
-        if advance:
-            self.iterations += 1
-
-    def device_iterations(self):
-        """The device counter (synchronises), or None while no step has run on the device path."""
-        if self._dev is None:
-            return None
-        return int(self._dev[0].item())
-
-    def state_dict(self, variables=None):
-        """`iterations` and, per variable in order (`variables`, default: in the order the
-        optimizer first saw them), the moments m and v on the CPU (None: no moments yet)."""
-        vs = list(self.state) if variables is None else list(variables)
-        c = lambda t: t.detach().to("cpu").clone()
-        sts = [self.state.get(v) for v in vs]
-        return {"iterations": self.iterations,
-                "m": [None if st is None else c(st[0]) for st in sts],
-                "v": [None if st is None else c(st[1]) for st in sts]}
-
-    @torch.no_grad()
-    def load_state_dict(self, sd, variables=None):
-        """Restore state_dict(): the host count, the device counter and the moments, written in
-        place where they exist (captured graphs hold their addresses)."""
-        vs = list(self.state) if variables is None else list(variables)
-        ms, ss = sd.get("m", []), sd.get("v", [])
-        if len(ms) != len(vs) or len(ss) != len(vs):
-            raise ValueError(f"TFAdam.load_state_dict: moments for {len(ms)} variables, have {len(vs)}")
-        for v, m, s in zip(vs, ms, ss):
-            st = self.state.get(v)
-            if m is None:
-                if st is not None:
-                    st[0].zero_(); st[1].zero_()
-                continue
-            if st is None:
-                st = self.state[v] = (torch.zeros_like(v), torch.zeros_like(v))
-            st[0].copy_(torch.as_tensor(m).to(st[0]))
-            st[1].copy_(torch.as_tensor(s).to(st[1]))
-        self.iterations = int(sd["iterations"])
-        if self._dev is not None:
-            self._dev[0] = self.iterations
-
-
-# HIP-graph captures are thread-local: with a torch.distributed "nccl" (RCCL) process group
-# alive, its watchdog thread queries events concurrently, and under the default global
-# capture mode such a query invalidates an ongoing capture ("operation failed due to a
-# previous error during capture", seen intermittently in round 3's RCCL test).
-_CAPTURE_MODE = "thread_local"
-
-
-class _GraphStep:
-    """An optimizer step (or one part of it) that a graph appends to its gradients in the
-    capture only: the graph constructors' warm-up runs apply no step.  prepare(grads), outside the
-    capture, makes what the launch needs and tells whether the optimizer's step can be captured
-    (TFAdam.prepare); calling it with the captured gradient buffers launches dpac_adam_step."""
-
-    def __init__(self, opt, variables, advance=True, snap=False):
-        """snap: the step reads the counter's snapshot (TFAdam.launch) and leaves the counter."""
-        self.opt, self.variables, self.advance, self.snap = opt, list(variables), advance, snap
-
-    def prepare(self, grads) -> bool:
-        return self.opt.prepare(zip(grads, self.variables))
-
-    def __call__(self, grads):
-        self.opt.launch(zip(grads, self.variables), self.advance, self.snap)
-
-
-class _GradGraph:
-    """One gradient evaluation (forward + backward) captured as a HIP graph over static
-    input buffers, with the optimizer step on those gradients at its end when `step` (a
-    _GraphStep) is given and can be captured (`stepped`); otherwise the optimizer runs
-    eagerly on the returned gradients, whose buffers the next replay overwrites.
-    Replaying it after copying a fresh batch in replaces the ~10^3 kernel launches of a
-    step (the actor's reverse time loop, the critic's G network and TD assembly) with one
-    graph launch.  Parameters are updated in place, so every replay sees the current
-    weights."""
-
-    def __init__(self, fn, batch: TrajectoryBatch, step=None):
-        self.static = TrajectoryBatch(*[t.clone() for t in batch])
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):  # warm-up outside the capture (allocator, autograd)
-            for _ in range(2):
-                out = fn(self.static)
-        torch.cuda.current_stream().wait_stream(side)
-        self.stepped = step is not None and step.prepare(out)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, capture_error_mode=_CAPTURE_MODE):
-            self.out = fn(self.static)
-            if self.stepped:
-                step(self.out)
-
-    def __call__(self, batch: TrajectoryBatch):
-        for dst, src in zip(self.static, batch):
-            dst.copy_(src)
-        self.graph.replay()
-        return list(self.out)
-
-
-def _capture_redo(fns):
-    """The deferred range-guard fallbacks a capture collected (ops.deferred_fallbacks) as one
-    HIP graph, or None when there are none: no-op kernels while the split-fp16 status word
-    is clear, the exact-f32 recomputation of their chains once it is set."""
-    if not fns:
-        return None
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, capture_error_mode=_CAPTURE_MODE):
-        for f in fns:
-            f()
-    return g
-
-
-class _SplitActorGraphs:
-    """The actor step as two HIP graphs: the fused forward rollout with its backward
-    saves (replayed on a side stream, so it runs beside the critic step: it reads only
-    the actor's parameters, which the critic step does not change) and the gradient
-    from those saves (after the critic update, which the terminal value V(x_N) needs;
-    solver.py:67-70 order).  The backward graph reads the forward graph's outputs in
-    place: nothing is copied between them.  With `step` (a _GraphStep that can be captured:
-    `stepped`) the actor's optimizer step ends the backward graph, behind its guard fallbacks."""
-
-    def __init__(self, fwd_fn, bwd_fn, batch: TrajectoryBatch, side, defer=None, step=None):
-        """defer: a context manager factory yielding the list the backward's deferred guard
-        fallbacks go to (ActorCriticSolver._deferring); they become the graph g_redo."""
-        self.static = TrajectoryBatch(*[t.clone() for t in batch])
-        self.side = side
-        defer = defer or (lambda: contextlib.nullcontext([]))
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):  # warm-up outside the capture (allocator, autograd)
-            for _ in range(2):
-                with defer() as fns:
-                    out = bwd_fn(fwd_fn(self.static))
-                for f in fns:
-                    f()
-        torch.cuda.current_stream().wait_stream(side)
-        self.stepped = step is not None and step.prepare(out)
-        self.g_fwd, self.g_bwd = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.g_fwd, capture_error_mode=_CAPTURE_MODE):
-            self.fwd = fwd_fn(self.static)
-        with torch.cuda.graph(self.g_bwd, capture_error_mode=_CAPTURE_MODE):
-            with defer() as self.redo_fns:
-                self.out = bwd_fn(self.fwd)
-            if not GUARD_DEFER_JOIN:  # the fallbacks at the chain's end, in the same graph
-                for f in self.redo_fns:
-                    f()
-                if self.stepped:
-                    step(self.out)
-        # DPAC_GUARD_DEFER=join: the step reads the gradients behind the joined fallbacks
-        tail = [lambda: step(self.out)] if self.stepped else []
-        self.g_redo = _capture_redo(list(self.redo_fns) + tail) if GUARD_DEFER_JOIN else None
-
-    def launch_forward(self, batch: TrajectoryBatch):
-        """On the side stream, after the work queued so far on the current stream."""
-        self.side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(self.side):
-            for dst, src in zip(self.static, batch):
-                if dst.data_ptr() != src.data_ptr():  # drawn in place by prefetch_samples: no copy
-                    dst.copy_(src)
-            self.g_fwd.replay()
-
-    def grads(self):
-        """The gradients (valid once redo() has run after them)."""
-        torch.cuda.current_stream().wait_stream(self.side)
-        self.g_bwd.replay()
-        return list(self.out)
-
-    def redo(self):
-        """The backward's deferred guard fallbacks (and then the captured step), on the current
-        stream (DPAC_GUARD_DEFER=join; otherwise they ended the backward graph)."""
-        if self.g_redo is not None:
-            self.g_redo.replay()
-
-
-class _SplitCriticGraphs:
-    """The critic step as three HIP graphs, split at the G network's output: the head
-    (rollout, G forward with saves, TD assembly, V forward, the loss's gradient at V's
-    output and at G's TD1 dots), V's backward (its parameter gradients), and the G
-    network's backward (input-gradient chain + parameter gradients).  The G backward reads
-    only the head's outputs, so it is launched on a side stream as soon as the head is done:
-    it runs beside V's backward, V's Adam step and the actor's terminal V(x_N) (a chain of
-    small kernels that leaves most CUs idle) and then beside the actor's BPTT, which needs
-    the updated V only (solver.py:221), not G.
-
-    With v_step and g_step (_GraphSteps that can be captured: `stepped`) the critic's optimizer
-    step is captured in its two parts: V's ends V's backward graph and G's, which advances the
-    step counter, ends G's backward graph on the side stream.  The two are not ordered with each
-    other (DPAC_GBACK=early launches the G backward before V's step), so V's part reads t from a
-    snapshot of the counter that the head graph takes before either can run: the advance cannot
-    reach what V's part reads."""
-
-    def __init__(self, head_fn, v_fn, back_fn, batch: TrajectoryBatch, side, defer=None,
-                 v_step=None, g_step=None):
-        """defer: as _SplitActorGraphs's, for the G backward (graph g_redo)."""
-        self.static = TrajectoryBatch(*[t.clone() for t in batch])
-        self.side = side
-        defer = defer or (lambda: contextlib.nullcontext([]))
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):  # warm-up outside the capture (allocator, autograd)
-            for _ in range(2):
-                h = head_fn(self.static)
-                gv = v_fn(h[0])
-                with defer() as fns:
-                    gb = back_fn((None,) + tuple(h[1]))
-                for f in fns:
-                    f()
-        torch.cuda.current_stream().wait_stream(side)
-        self.stepped = (v_step is not None and g_step is not None and v_step.prepare(gv)
-                        and g_step.prepare(gb))
-        self.g_head, self.g_v, self.g_back = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.g_head, capture_error_mode=_CAPTURE_MODE):
-            if self.stepped:  # this step's t for V's part, before G's part can advance the counter
-                v_step.opt.snapshot()
-            self.head_out = head_fn(self.static)
-        with torch.cuda.graph(self.g_v, capture_error_mode=_CAPTURE_MODE):
-            self.v_out = v_fn(self.head_out[0])
-            if self.stepped:
-                v_step(self.v_out)
-        with torch.cuda.graph(self.g_back, capture_error_mode=_CAPTURE_MODE):
-            with defer() as self.redo_fns:
-                self.back_out = back_fn((None,) + tuple(self.head_out[1]))
-            if not GUARD_DEFER_JOIN:  # the fallbacks at the chain's end, on the side stream
-                for f in self.redo_fns:
-                    f()
-                if self.stepped:
-                    g_step(self.back_out)
-        # DPAC_GUARD_DEFER=join: G's step behind the joined fallbacks, on the current stream
-        tail = [lambda: g_step(self.back_out)] if self.stepped else []
-        self.g_redo = _capture_redo(list(self.redo_fns) + tail) if GUARD_DEFER_JOIN else None
-
-    def head(self, batch: TrajectoryBatch):
-        """The head graph on the current stream."""
-        for dst, src in zip(self.static, batch):
-            if dst.data_ptr() != src.data_ptr():  # drawn in place by prefetch_samples: no copy
-                dst.copy_(src)
-        self.g_head.replay()
-
-    def grads_v(self):
-        """V's parameter gradients, and then V's captured step (current stream, after head())."""
-        self.g_v.replay()
-        return list(self.v_out)
-
-    def launch_back(self, after: torch.cuda.Event):
-        """G's parameter gradients (and then G's captured step), replayed on the side stream once
-        `after` (recorded behind head()) has passed; use them on the side stream (valid once
-        redo() has run)."""
-        self.side.wait_event(after)
-        with torch.cuda.stream(self.side):
-            self.g_back.replay()
-        return list(self.back_out)
-
-    def redo(self):
-        """The G backward's deferred guard fallbacks (and then G's captured step), on the current
-        stream after it has waited for the side stream (DPAC_GUARD_DEFER=join; otherwise they
-        ended the backward graph)."""
-        if self.g_redo is not None:
-            self.g_redo.replay()
-
 
 # DPAC_GRAPH_SETS=2: train_iteration alternates two sets of the split graphs and prefetch_samples
 # draws the next iteration's samples into the idle set's static inputs (no copies in front of the
@@ -704,6 +288,8 @@ GUARD_DEFER_JOIN = _GD_ENV == "join"
 # iteration then holds three of the box's four hardware queues, leaving one to RCCL's stream at
 # N > 1) or "own" (a stream of its own, rounds 4-5)
 SAMPLE_STREAM = os.environ.get("DPAC_SAMPLE_STREAM", "gside")
+if SAMPLE_STREAM not in ("gside", "own"):
+    raise ValueError(f"DPAC_SAMPLE_STREAM must be 'gside' or 'own', got {SAMPLE_STREAM!r}")
 
 # DPAC_GBACK=late (default): the critic's G backward is launched on its side stream after V's
 # update and the actor's BPTT are queued, so it runs beside the BPTT and the actor's
@@ -772,26 +358,17 @@ class ActorCriticSolver(object):
         self.par.broadcast_(self.critic_variables() + self.actor_variables())
         nc = self.net_config
         self.optimizer_critic = TFAdam(PiecewiseConstantDecay(nc.lr_boundaries_critic, nc.lr_values_critic),
-                                       epsilon=1e-8)
+                                       epsilon=1e-8, device_schedule=ADAM == "device")
         self.optimizer_actor = TFAdam(PiecewiseConstantDecay(nc.lr_boundaries_actor, nc.lr_values_actor),
-                                      epsilon=1e-8)
-        self.x = None
-        self.gamma = self.eqn_config.discount
-        st = self.train_config.sample_type
+                                      epsilon=1e-8, device_schedule=ADAM == "device")
+        st =self.train_config.sample_type
         if st not in ("normal", "bounded"):
             raise ValueError(f"sample_type must be 'normal' or 'bounded', got {st!r}")
         self.sample_type = st
-        if self.train_config.train == "actor-critic":
-            self.cheat_value_in_actor = False
-            self.cheat_control_in_critic = False
-        elif self.train_config.train == "critic":
-            self.cheat_control_in_critic = True
-            self.cheat_value_in_actor = False
-        elif self.train_config.train == "actor":
-            self.cheat_value_in_actor = True
-            self.cheat_control_in_critic = False
-        else:
+        if self.train_config.train not in ("actor-critic", "critic", "actor"):
             raise ValueError(f"unknown train mode {self.train_config.train!r}")
+        self.cheat_control_in_critic = self.train_config.train == "critic"
+        self.cheat_value_in_actor = self.train_config.train == "actor"
         self._calls = 0
         self._next_samples = None  # (spec, critic batch, actor batch, ready event)
         self._sample_side = None
@@ -816,9 +393,6 @@ class ActorCriticSolver(object):
             yield self._redo_sink
         finally:
             self._redo_sink = prev
-
-    def _defer(self):
-        return self._deferring if GUARD_DEFER else None
 
     # ---- variables ---------------------------------------------------------
     def critic_variables(self):
@@ -916,38 +490,45 @@ class ActorCriticSolver(object):
         loss = self.loss_actor(inputs, training, cheat_value, cheat_control)
         return list(torch.autograd.grad(loss, vs, allow_unused=True))
 
-    def _global(self, data, total):
-        return data.x0.shape[0], total
+    def _capture_steps(self, opt):
+        """Whether opt's steps go inside the graphs: its schedule on the device and no process
+        group (with one, also one of a single rank, the all-reduce sits between the gradients
+        and the step)."""
+        return self.hip_graphs and isinstance(self.par, SingleProcess) and opt.device_schedule
 
-    def _capture_steps(self):
-        """Whether the optimizer steps go inside the graphs: the schedule on the device and no
-        process group (with one, also one of a single rank, the all-reduce sits between the
-        gradients and the step)."""
-        return self.hip_graphs and isinstance(self.par, SingleProcess) and ADAM == "device"
+    def _step(self, opt, grads, variables, applied, count=None, advance=True):
+        """opt's step on `variables`, or with advance=False a part of one that does not count.
+        applied: a graph replay already ran it and the host only counts it; otherwise apply it
+        to `grads`, all-reduced first over count = (this rank's rows, all ranks') when given."""
+        if applied:
+            if advance:
+                opt.iterations += 1
+            return
+        if count is not None:
+            grads = self.par.allreduce_grads(grads, *count)
+        opt.apply_gradients(zip(grads, variables), advance=advance)
 
-    def _grads(self, kind, fn, data, opt=None, variables=None):
-        """fn(batch) -> (gradients, whether the graph applied opt's step on them), through a
-        captured HIP graph when enabled."""
+    def _train_step(self, kind, fn, opt, variables, data, total):
+        """One unsplit step: fn(batch) -> gradients, through a captured HIP graph when enabled
+        (with opt's step at its end when that can be captured), then _step."""
+        cnt = data[0].shape[0]
         data = Equation.to_native(data, self.dtype)
-        if not self.hip_graphs:
-            return fn(data), False
-        key = (kind, tuple(data.dw.shape))
-        graph = self._graphs.get(key)
-        if graph is None:
-            step = _GraphStep(opt, variables) if opt is not None and self._capture_steps() else None
-            graph = self._graphs[key] = _GradGraph(fn, data, step)
-        return graph(data), graph.stepped
+        graph = self._graphs.get((kind, tuple(data.dw.shape)))
+        if graph is None and self.hip_graphs:
+            step = _GraphStep(opt, variables) if self._capture_steps(opt) else None
+            graph = self._graphs[kind, tuple(data.dw.shape)] = _GradGraph(fn, data, step)
+        g = fn(data) if graph is None else graph(data)
+        self._step(opt, g, variables, graph is not None and graph.stepped, (cnt, total or cnt * self.par.world))
 
     def train_step_critic(self, train_data, total=None):
-        g, stepped = self._grads("critic", lambda d: self.grad_critic(
-            d, training=False, cheat_control=self.cheat_control_in_critic), train_data,
-            self.optimizer_critic, self.critic_variables())
-        if stepped:  # applied by the replay; the host only counts it
-            self.optimizer_critic.iterations += 1
-            return
-        cnt = train_data[0].shape[0]
-        g = self.par.allreduce_grads(g, cnt, total or cnt * self.par.world)
-        self.optimizer_critic.apply_gradients(zip(g, self.critic_variables()))
+        self._train_step("critic", lambda d: self.grad_critic(
+            d, training=False, cheat_control=self.cheat_control_in_critic),
+            self.optimizer_critic, self.critic_variables(), train_data, total)
+
+    def train_step_actor(self, train_data, total=None):
+        self._train_step("actor", lambda d: self.grad_actor(
+            d, training=False, cheat_value=self.cheat_value_in_actor, cheat_control=False),
+            self.optimizer_actor, self.actor_variables(), train_data, total)
 
     # ---- the actor step split around the critic step (overlap) ---------------
     def _actor_split_ok(self):
@@ -1082,6 +663,21 @@ class ActorCriticSolver(object):
                                             False, True, ws_tag=1, mask=m)
         return grads
 
+    def _actor_graphs(self, da):
+        oa = self.optimizer_actor
+        step = _GraphStep(oa, self.actor_variables()) if self._capture_steps(oa) else None
+        return _SplitActorGraphs(self.actor_forward, self.actor_grads_from, da, self._side,
+                                 self._deferring if GUARD_DEFER else None, step, GUARD_DEFER_JOIN)
+
+    def _critic_graphs(self, dc):
+        mc, oc = self.model_critic, self.optimizer_critic
+        cap = self._capture_steps(oc)
+        return _SplitCriticGraphs(
+            self.critic_head, self.critic_grads_v, self.critic_G_back, dc, self._side_g,
+            self._deferring if GUARD_DEFER else None,
+            _GraphStep(oc, mc.NN_value.trainable_variables(), snap=True) if cap else None,
+            _GraphStep(oc, mc.NN_value_grad.trainable_variables()) if cap else None, GUARD_DEFER_JOIN)
+
     def train_iteration(self, data_critic, data_actor, total=None):
         """One iteration of solver.py:67-70 (critic step, then actor step).  With HIP
         graphs the actor's forward rollout runs on a side stream during the critic step;
@@ -1091,12 +687,13 @@ class ActorCriticSolver(object):
         solver.py:221), then the actor's gradients and G's half in one flattened exchange (G
         is next read by the following iteration's critic step).
 
-        Without a process group and with ADAM == "device" the three optimizer launches are inside the graphs
-        (V's at the end of V's backward graph, the actor's at the end of its backward graph, G's
-        at the end of G's backward graph on its side stream): once the graphs exist the host launches no
-        optimizer kernel and only counts the steps.  The streams that next read a network are
-        behind its step: this stream runs V's and the actor's and waits for the G side stream
-        before the iteration ends, and the next forward rollout's side stream waits for this one."""
+        When the steps are captured (_capture_steps) the three optimizer launches are inside the
+        graphs (V's at the end of V's backward graph, the actor's at the end of its backward graph,
+        G's at the end of G's backward graph on its side stream): once the graphs exist the host
+        launches no optimizer kernel and only counts the steps (_step).  The streams that next
+        read a network are behind its step: this stream runs V's and the actor's and waits for the
+        G side stream before the iteration ends, and the next forward rollout's side stream waits
+        for this one."""
         if not self._actor_split_ok():
             self.train_step_critic(data_critic, total)
             self.train_step_actor(data_actor, total)
@@ -1104,90 +701,53 @@ class ActorCriticSolver(object):
         da = Equation.to_native(data_actor, self.dtype)
         if self._side is None:
             self._side = torch.cuda.Stream()
-        cap = self._capture_steps()
         oa, oc = self.optimizer_actor, self.optimizer_critic
-        astep = lambda: _GraphStep(oa, self.actor_variables()) if cap else None
-        if not self._critic_split_ok():
+        cnt = da.x0.shape[0]
+        acount = (cnt, total or cnt * self.par.world)
+        if not self._critic_split_ok():  # the actor step split around the unsplit critic step
             key = ("actor_split", tuple(da.dw.shape))
             sg = self._graphs.get(key)
             if sg is None:
-                sg = self._graphs[key] = _SplitActorGraphs(self.actor_forward, self.actor_grads_from,
-                                                           da, self._side, self._defer(), astep())
+                sg = self._graphs[key] = self._actor_graphs(da)
             sg.launch_forward(da)
             self.train_step_critic(data_critic, total)
-            cg = None
-        else:
-            dc = Equation.to_native(data_critic, self.dtype)
-            if self._side_g is None:
-                self._side_g = torch.cuda.Stream()
-            spec = (dc.x0.shape[0] * self.par.world if total is None else total, dc.dw.shape[0], da.dw.shape[0])
-            sets = self._gsets.setdefault(spec, [None, None])
-            p = self._parity
-            if sets[p] is None:
-                mc = self.model_critic
-                sets[p] = (_SplitActorGraphs(self.actor_forward, self.actor_grads_from, da, self._side,
-                                             self._defer(), astep()),
-                           _SplitCriticGraphs(
-                               self.critic_head, self.critic_grads_v, self.critic_G_back, dc,
-                               self._side_g, self._defer(),
-                               _GraphStep(oc, mc.NN_value.trainable_variables(), snap=True) if cap else None,
-                               _GraphStep(oc, mc.NN_value_grad.trainable_variables()) if cap else None))
-            sg, cg = sets[p]
-            sg.launch_forward(da)
-            ccnt = dc.x0.shape[0]
-            ctot = total or ccnt * self.par.world
-            cg.head(dc)
-            head_done = torch.cuda.Event()
-            head_done.record()
-            if GBACK == "early":  # G's backward beside V's update and the actor's terminal V
-                gG = cg.launch_back(head_done)
-            gV = cg.grads_v()
-            # one Adam step of the critic in two parts: V now (the actor reads it), G after the
-            # actor's exchange (same lr and t: advance=False here)
-            if not cg.stepped:  # (captured: V's part ended the graph)
-                gV = self.par.allreduce_grads(gV, ccnt, ctot)
-                oc.apply_gradients(zip(gV, self.model_critic.NN_value.trainable_variables()), advance=False)
-        g = sg.grads()  # the actor's terminal V(x_N), BPTT and parameter gradients
-        cnt = da.x0.shape[0]
-        atot = total or cnt * self.par.world
-        if cg is None:
-            sg.redo()
-            if sg.stepped:
-                oa.iterations += 1
-                return
-            g = self.par.allreduce_grads(g, cnt, atot)
-            oa.apply_gradients(zip(g, self.actor_variables()))
+            g = sg.grads()  # the actor's terminal V(x_N), BPTT and parameter gradients
+            sg.chain.redo()
+            self._step(oa, g, self.actor_variables(), sg.stepped, acount)
             return
+        dc = Equation.to_native(data_critic, self.dtype)
+        if self._side_g is None:
+            self._side_g = torch.cuda.Stream()
+        ccnt = dc.x0.shape[0]
+        ccount = (ccnt, total or ccnt * self.par.world)
+        sets = self._gsets.setdefault((ccount[1], dc.dw.shape[0], da.dw.shape[0]), [None, None])
+        if sets[self._parity] is None:
+            sets[self._parity] = (self._actor_graphs(da), self._critic_graphs(dc))
+        sg, cg = sets[self._parity]
+        sg.launch_forward(da)
+        cg.head(dc)
+        head_done = torch.cuda.Event()
+        head_done.record()
+        if GBACK == "early":  # G's backward beside V's update and the actor's terminal V
+            gG = cg.launch_back(head_done)
+        gV = cg.grads_v()
+        # one Adam step of the critic in two parts: V now (the actor reads it), G after the
+        # actor's exchange (same lr and t: advance=False here)
+        self._step(oc, gV, self.model_critic.NN_value.trainable_variables(), cg.stepped, ccount, advance=False)
+        g = sg.grads()  # the actor's terminal V(x_N), BPTT and parameter gradients
         if GBACK != "early":
             gG = cg.launch_back(head_done)
         torch.cuda.current_stream().wait_stream(cg.side)  # G's gradients (and step), made on the side stream
-        sg.redo()  # DPAC_GUARD_DEFER=join: both chains' range-guard fallbacks (no-ops unless a split
-        cg.redo()  # operand overflowed); by default each chain's graph ends with its own
+        sg.chain.redo()  # DPAC_GUARD_DEFER=join: both chains' range-guard fallbacks (no-ops unless a
+        cg.chain.redo()  # split operand overflowed); by default each chain's graph ends with its own
         if not (sg.stepped and cg.stepped):
-            g, gG = self.par.allreduce_grads_multi([(g, cnt, atot), (gG, ccnt, ctot)])
-        if sg.stepped:
-            oa.iterations += 1
-        else:
-            oa.apply_gradients(zip(g, self.actor_variables()))
-        if cg.stepped:
-            oc.iterations += 1
-        else:
-            oc.apply_gradients(zip(gG, self.model_critic.NN_value_grad.trainable_variables()))
+            g, gG = self.par.allreduce_grads_multi([(g, *acount), (gG, *ccount)])
+        self._step(oa, g, self.actor_variables(), sg.stepped)
+        self._step(oc, gG, self.model_critic.NN_value_grad.trainable_variables(), cg.stepped)
         done = torch.cuda.Event()  # every reader of this set's static inputs is behind this point
         done.record()
         self._set_done[self._parity] = done
         self._parity = (self._parity + 1) % graph_sets(ccnt)
-
-    def train_step_actor(self, train_data, total=None):
-        g, stepped = self._grads("actor", lambda d: self.grad_actor(
-            d, training=False, cheat_value=self.cheat_value_in_actor, cheat_control=False), train_data,
-            self.optimizer_actor, self.actor_variables())
-        if stepped:  # applied by the replay; the host only counts it
-            self.optimizer_actor.iterations += 1
-            return
-        cnt = train_data[0].shape[0]
-        g = self.par.allreduce_grads(g, cnt, total or cnt * self.par.world)
-        self.optimizer_actor.apply_gradients(zip(g, self.actor_variables()))
 
     # ---- save and restore ----------------------------------------------------
     def _nets(self):

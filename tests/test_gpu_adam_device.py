@@ -8,6 +8,8 @@ DPAC_ADAM=device), captured inside the solver's HIP graphs, against the host-sca
   production shape, and no optimizer launch from the host once the graphs exist;
 * save and restore: 3 + 3 iterations equal 6.
 """
+import weakref
+
 import numpy as np
 import pytest
 import torch
@@ -170,6 +172,8 @@ def _run(monkeypatch, adam, cfg, graphs, iters, seed=5, each=None):
             each(sp, i)
         _iterate(sp, cfg)
         out.append(_params(sp))
+    if adam == "host":  # the patch reached the optimizers: no step ever ran on the device path
+        assert sp.optimizer_critic.device_iterations() is None and sp.optimizer_actor.device_iterations() is None
     return sp, out
 
 
@@ -241,9 +245,55 @@ def test_production_shape_device_matches_host(monkeypatch, sets):
             sp.train_iteration(dc, da, 2048)
             sp.prefetch_samples(2048, 100, 100)
         assert sp._critic_split_ok()
+        assert sum(s is not None for v in sp._gsets.values() for s in v) == sets
+        if adam == "host":
+            assert sp.optimizer_critic.device_iterations() is None and sp.optimizer_actor.device_iterations() is None
         out[adam] = _params(sp)
+        # in no reference cycle: a solver left to the garbage collector could be freed, its HIP
+        # graphs destroyed, inside a later solver's capture, which aborts the process
+        gone = weakref.ref(sp)
+        del sp
+        assert gone() is None
     for a, b in zip(out["host"], out["device"]):
         assert torch.equal(a, b)
+
+
+GUARDS = [(False, False), (True, False), (True, True)]  # (GUARD_DEFER, GUARD_DEFER_JOIN)
+
+
+def test_actor_split_without_the_critic_split_all_guard_modes_and_both_adams(monkeypatch):
+    """train = "actor-critic" under TD2 with graphs: the actor step is split around the unsplit
+    critic step (one _SplitActorGraphs in sp._graphs, no graph set), so train_iteration replays the
+    actor chain's redo graph and then counts or applies the actor's step on its own.  4 iterations
+    at _small_cfg's shape under DPAC_GUARD_DEFER = 0, 1 and join, each with ADAM host and device:
+    all six bitwise equal, ops.x3_fell_back the same (clear).  At this shape the actor chain does
+    collect deferred fallbacks (two, before and after the chain moved to _BackwardChain: in float32
+    the split-fp16 range guard is on at every batch size), so the batch stays 96."""
+    cfg = _small_cfg("float32", "TD2")
+    runs = {}
+    for defer, join in GUARDS:
+        monkeypatch.setattr(psol, "GUARD_DEFER", defer)
+        monkeypatch.setattr(psol, "GUARD_DEFER_JOIN", join)
+        for adam in ("host", "device"):
+            ops.x3_status_reset("cuda")
+            sp, out = _run(monkeypatch, adam, cfg, True, 4)
+            assert sp._actor_split_ok() and not sp._critic_split_ok() and not sp._gsets
+            chain, = [g.chain for k, g in sp._graphs.items() if k[0] == "actor_split"]
+            assert bool(chain.redo_fns) == defer
+            assert chain.stepped == (adam == "device")
+            assert (chain.g_redo is not None) == join
+            assert sp.optimizer_actor.iterations == sp.optimizer_critic.iterations == 4
+            runs[defer, join, adam] = (out, ops.x3_fell_back("cuda"))
+            gone = weakref.ref(sp)  # in no reference cycle (test_production_shape_device_matches_host)
+            del sp, chain
+            assert gone() is None
+    want, fell = runs[False, False, "host"]
+    assert fell is False and any(not torch.equal(a, b) for a, b in zip(want[0], want[3]))
+    for key, (got, f) in runs.items():
+        assert f == fell, key
+        for i, (w, g) in enumerate(zip(want, got)):
+            for a, b in zip(w, g):
+                assert torch.equal(a, b), (key, i + 1)
 
 
 @pytest.mark.parametrize("dtype", ["float32", "float64"])

@@ -195,6 +195,12 @@ def _production_params(monkeypatch, attr, value, iters=4, big=None):
         sp.prefetch_samples(2048, 100, 100)
     torch.cuda.synchronize()
     assert sp._critic_split_ok()
+    # the patched knob reached the graphs the solver built
+    sets = [s for v in sp._gsets.values() for s in v if s is not None]
+    assert len(sets) == psol.graph_sets(2048) and (attr != "GRAPH_SETS" or len(sets) == value)
+    for chain in (c for sg, cg in sets for c in (sg.chain, cg.chain)):
+        assert (chain.g_redo is not None) == psol.GUARD_DEFER_JOIN
+        assert psol.GUARD_DEFER or chain.redo_fns == []
     fell = ops.x3_fell_back("cuda")
     ops.x3_status_reset("cuda")
     return [v.detach().cpu().clone() for v in sp.critic_variables() + sp.actor_variables()], fell
