@@ -24,22 +24,16 @@ EQNS      := lqr lqrvar ekn vdp
 HDRS      :=
 eqn_dims   = $(if $(filter vdp,$(1)),$(EVEN_LIST),$(DIM_LIST))
 EQN_OBJS  := $(foreach e,$(EQNS),$(foreach d,$(call eqn_dims,$(e)),$(foreach t,f32 f64,$(OBJDIR)/dpac_eqn_$(e)_$(t)_d$(d).o)))
-OBJS      := $(OBJDIR)/dpac_abi.o $(OBJDIR)/dpac_mlp.o $(OBJDIR)/dpac_params.o $(EQN_OBJS)
+CORE_OBJS := $(OBJDIR)/dpac_abi.o $(OBJDIR)/dpac_mlp.o $(OBJDIR)/dpac_params.o $(OBJDIR)/dpac_sample.o
+OBJS      := $(CORE_OBJS) $(EQN_OBJS)
 LIB       := $(PKG)/libdpac.so
 
 .PHONY: all lib ext plugins bounds clean
 all: lib
 lib: $(LIB)
 
-$(OBJDIR)/dpac_abi.o: $(CSRC)/dpac_abi.hip $(HDRS)
-	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(OBJDIR)/dpac_mlp.o: $(CSRC)/dpac_mlp.hip $(HDRS)
-	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(OBJDIR)/dpac_params.o: $(CSRC)/dpac_params.hip $(HDRS)
+# the units that are compiled once: the ABI layer, the MLP row kernels, Adam / prepare, the sampler
+$(CORE_OBJS): $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -94,7 +88,7 @@ ASAN_DIR  := build/asan
 ASAN_HOST := -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined \
              -Xarch_host -fno-omit-frame-pointer -Xarch_host -fno-sanitize-recover=undefined
 ASAN_FLAGS := $(filter-out -DDPAC_DIMS=% -DDPAC_DIMS_EVEN=%,$(HIPFLAGS)) -DDPAC_DIMS=20 -DDPAC_DIMS_EVEN=20 -O1 $(ASAN_HOST)
-ASAN_OBJS := $(ASAN_DIR)/dpac_abi.o $(ASAN_DIR)/dpac_mlp.o $(ASAN_DIR)/dpac_params.o \
+ASAN_OBJS := $(ASAN_DIR)/dpac_abi.o $(ASAN_DIR)/dpac_mlp.o $(ASAN_DIR)/dpac_params.o $(ASAN_DIR)/dpac_sample.o \
              $(foreach e,$(EQNS),$(ASAN_DIR)/dpac_eqn_$(e)_f32.o $(ASAN_DIR)/dpac_eqn_$(e)_f64.o)
 CLANG     ?= /opt/rocm/llvm/bin/clang
 SANRT     := $(dir $(firstword $(wildcard /opt/rocm/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.so)))

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DPAC_LIB", os.path.join(_HERE, "libdpac.so"))
 
 # constants mirrored from include/dpac.h
-ABI_VERSION = 9  # DPAC_ABI_VERSION: load() refuses a library built from another header
+ABI_VERSION = 10  # DPAC_ABI_VERSION: load() refuses a library built from another header
 DPAC_OK, DPAC_EINVAL, DPAC_EUNSUP = 0, -1, -2
 F32, F64 = 0, 1
 EQN_LQR, EQN_VDP, EQN_EKN, EQN_LQR_VAR = 0, 1, 2, 3
@@ -74,7 +74,8 @@ class Mlp(ctypes.Structure):
 
 _P = ctypes.c_void_p
 _I32, _I64, _U64, _D = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_double
-_EQ = ctypes.POINTER(EqnParams)
+_EQ, _MLP = ctypes.POINTER(EqnParams), ctypes.POINTER(Mlp)
+_PP, _PI32, _PI64 = ctypes.POINTER(_P), ctypes.POINTER(_I32), ctypes.POINTER(_I64)
 
 # name -> argtypes (restype int unless listed in _RESTYPES)
 SIGNATURES = {
@@ -96,43 +97,24 @@ SIGNATURES = {
     "dpac_td_assemble_bwd_gdot": [_EQ, _I32, _I64, _I32, _P, _P, _P, _P, _P],
     "dpac_actor_cost_fwd": [_EQ, _I32, _I64, _I32, _P, _P, _P, _P, _P, _P, _P],
     "dpac_equation_eval": [_EQ, _I32, _I32, _I64, _P, _P, _P, _P],
-    "dpac_rollout_nn_fwd": [_EQ, _I32, _I32, _I64, _I32, _D, ctypes.POINTER(Mlp), _P, _P, _P, _P,
-                            _P, _P, _I32, _P, _P, _P, _P, _P, _P],
-    "dpac_rollout_nn_bwd": [_EQ, _I32, _I32, _I64, _I32, _D, ctypes.POINTER(Mlp),
-                            ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), _P, _P,
-                            _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
-    "dpac_rollout_nn_mask_tile_bytes": [ctypes.POINTER(Mlp)],
-    "dpac_rollout_nn_mask_bytes": [ctypes.POINTER(Mlp), _I32, _I64, _I32],
-    "dpac_rollout_nn_fwd_masked": [_EQ, _I32, _I32, _I64, _I32, _D, ctypes.POINTER(Mlp), _P, _P, _P, _P,
-                                   _P, _P, _I32, _P, _P, _P, _P, _P, _P, ctypes.POINTER(_I32), _P],
-    "dpac_rollout_nn_bwd_masked": [_EQ, _I32, _I32, _I64, _I32, _D, ctypes.POINTER(Mlp),
-                                   ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), _P, _P,
-                                   _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
-    "dpac_mlp_rows_fwd": [_I32, _I64, ctypes.POINTER(Mlp), _P, _I64, _P, _P, _P],
-    "dpac_mlp_rows_bwd": [_I32, _I64, ctypes.POINTER(Mlp), ctypes.POINTER(ctypes.c_void_p),
-                          ctypes.POINTER(ctypes.c_void_p), _P, _P, _P, _P, _P],
-    "dpac_mlp_rows_fwd_td1": [_EQ, _I32, _I64, ctypes.POINTER(Mlp), _P, _I64, _P, _P, _P, _P, _P],
-    "dpac_mlp_rows_bwd_td1": [_EQ, _I32, _I64, ctypes.POINTER(Mlp), ctypes.POINTER(ctypes.c_void_p),
-                              ctypes.POINTER(ctypes.c_void_p), _P, _P, _I64, _P, _P, _P, _P, _P, _P],
-    "dpac_mlp_rows_mask_bytes": [ctypes.POINTER(Mlp), _I32, _I64],
-    "dpac_mlp_rows_fwd_masked": [_I32, _I64, ctypes.POINTER(Mlp), _P, _I64, _P, _P, _P, ctypes.POINTER(_I32), _P],
-    "dpac_mlp_rows_bwd_masked": [_I32, _I64, ctypes.POINTER(Mlp), ctypes.POINTER(ctypes.c_void_p),
-                                 ctypes.POINTER(ctypes.c_void_p), _P, _P, _P, _P, _P, _P],
-    "dpac_mlp_rows_fwd_td1_masked": [_EQ, _I32, _I64, ctypes.POINTER(Mlp), _P, _I64, _P, _P, _P, _P, _P,
-                                     ctypes.POINTER(_I32), _P],
-    "dpac_mlp_rows_bwd_td1_masked": [_EQ, _I32, _I64, ctypes.POINTER(Mlp), ctypes.POINTER(ctypes.c_void_p),
-                                     ctypes.POINTER(ctypes.c_void_p), _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P],
-    "dpac_mlp_param_grads_workspace": [_I32, _I64, ctypes.POINTER(Mlp)],
-    "dpac_mlp_param_grads": [_I32, _I64, ctypes.POINTER(Mlp), _D, _P, _I64, _P, _P, _P, _I64, _P,
-                             _P],
-    "dpac_mlp_prepare": [_I32, ctypes.POINTER(Mlp), _D, _P, _P, _P, _P, _P, _P, _P],
+    "dpac_rollout_nn_mask_tile_bytes": [_MLP],
+    "dpac_rollout_nn_mask_bytes": [_MLP, _I32, _I64, _I32],
+    "dpac_rollout_nn_fwd": [_EQ, _I32, _I32, _I64, _I32, _D, _MLP, _P, _P, _P, _P, _P, _P, _I32, _P,
+                            _P, _P, _P, _P, _P, _PI32, _P],
+    "dpac_rollout_nn_bwd": [_EQ, _I32, _I32, _I64, _I32, _D, _MLP, _PP, _PP, _P, _P, _P, _P, _P, _P,
+                            _P, _P, _P, _P, _P, _P, _P],
+    "dpac_mlp_rows_mask_bytes": [_MLP, _I32, _I64],
+    "dpac_mlp_rows_fwd": [_I32, _I64, _MLP, _P, _I64, _P, _P, _P, _PI32, _P],
+    "dpac_mlp_rows_bwd": [_I32, _I64, _MLP, _PP, _PP, _P, _P, _P, _P, _P, _P],
+    "dpac_mlp_rows_fwd_td1": [_EQ, _I32, _I64, _MLP, _P, _I64, _P, _P, _P, _P, _P, _PI32, _P],
+    "dpac_mlp_rows_bwd_td1": [_EQ, _I32, _I64, _MLP, _PP, _PP, _P, _P, _P, _I64, _P, _P, _P, _P,
+                              _P, _P],
+    "dpac_mlp_param_grads_workspace": [_I32, _I64, _MLP],
+    "dpac_mlp_param_grads": [_I32, _I64, _MLP, _D, _P, _I64, _P, _P, _P, _I64, _P, _P],
+    "dpac_mlp_prepare": [_I32, _MLP, _D, _P, _P, _P, _P, _P, _P, _P],
     "dpac_critic_loss_grad": [_I32, _I64, _P, _P, _P, _P, _D, _D, _P, _P, _P],
-    "dpac_adam_apply": [_I32, _I32, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_void_p),
-                        ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
-                        ctypes.POINTER(ctypes.c_void_p), _D, _D, _D, _D, _P],
-    "dpac_adam_step": [_I32, _I32, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_void_p),
-                       ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
-                       ctypes.POINTER(ctypes.c_void_p), _P, _P, _I64, _D, _D, _D, _I32, _P],
+    "dpac_adam_apply": [_I32, _I32, _PI64, _PP, _PP, _PP, _PP, _D, _D, _D, _D, _P],
+    "dpac_adam_step": [_I32, _I32, _PI64, _PP, _PP, _PP, _PP, _P, _P, _I64, _D, _D, _D, _I32, _P],
 }
 _RESTYPES = {"dpac_abi_version": ctypes.c_int32, "dpac_last_error": ctypes.c_char_p,
              "dpac_supported": ctypes.c_int32, "dpac_mlp_param_grads_workspace": ctypes.c_int64,
@@ -255,17 +237,31 @@ def _load_new_plugins():
     return lib
 
 
+def _raise(lib, name: str, rc: int):
+    msg = lib.dpac_last_error()
+    text = msg.decode() if msg else ""
+    if rc == DPAC_EUNSUP and "no kernel instantiation for dim" in text:
+        text += (" (build a dimension plugin: `make ext EXT_DIMS=<dim>` or "
+                 "deeppde_actorcritic_amd._lib.build_dim_plugin(<dim>))")
+    raise DpacError(name, rc, text)
+
+
 def call(name: str, *args) -> None:
     """Call an entry point and raise DpacError on a non-zero status."""
     lib = load()
     rc = getattr(lib, name)(*args)
     if rc != DPAC_OK:
-        msg = lib.dpac_last_error()
-        text = msg.decode() if msg else ""
-        if rc == DPAC_EUNSUP and "no kernel instantiation for dim" in text:
-            text += (" (build a dimension plugin: `make ext EXT_DIMS=<dim>` or "
-                     "deeppde_actorcritic_amd._lib.build_dim_plugin(<dim>))")
-        raise DpacError(name, rc, text)
+        _raise(lib, name, rc)
+
+
+def query(name: str, *args) -> int:
+    """Call a size query (a count of bytes, negative on a bad argument) and return its value;
+    raise DpacError on a negative one."""
+    lib = load()
+    n = int(getattr(lib, name)(*args))
+    if n < 0:
+        _raise(lib, name, n)
+    return n
 
 
 def exported_symbols() -> list:

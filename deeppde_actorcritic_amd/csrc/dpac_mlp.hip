@@ -5,6 +5,7 @@
 
 #include <cstdlib>
 
+#include "dpac_host.h"
 #include "dpac_mlp_grad.h"
 #include "dpac_mlp_grad_x3.h"
 #include "dpac_mlp_rows.h"

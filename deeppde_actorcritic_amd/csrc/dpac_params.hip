@@ -27,6 +27,7 @@
 
 #include "dpac.h"
 #include "dpac_device.h"
+#include "dpac_host.h"
 
 namespace dpac {
 

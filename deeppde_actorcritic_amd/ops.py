@@ -51,6 +51,11 @@ def _dtype_id(t: torch.Tensor) -> int:
         raise TypeError(f"libdpac supports float32/float64, got {t.dtype}") from None
 
 
+def _u64(seed: int) -> int:
+    """A Python int seed as the ABI's uint64_t."""
+    return seed & 0xFFFFFFFFFFFFFFFF
+
+
 def _check_same(ref: torch.Tensor, *others):
     for o in others:
         if o is not None and (o.dtype != ref.dtype or o.device != ref.device):
@@ -81,8 +86,20 @@ def sample(eqp, sample_type: int, num_sample: int, num_steps: int, seed: int,
         x_bdry = torch.empty(num_sample, d, dtype=dtype, device=device)
         dw = torch.empty(num_steps, num_sample, d, dtype=dtype, device=device) if want_dw else None
     call("dpac_sample", ctypes.byref(eqp), sample_type, _DT[dtype], num_sample, num_steps,
-         seed & 0xFFFFFFFFFFFFFFFF, traj_offset, _ptr(x0), _ptr(dw), _ptr(x_bdry), _stream(x0))
+         _u64(seed), traj_offset, _ptr(x0), _ptr(dw), _ptr(x_bdry), _stream(x0))
     return x0, dw, x_bdry
+
+
+def _rollout_outputs(eqp, x0, N: int, want_u: bool, want_cost: bool, out=None):
+    """The outputs of a fused rollout from x0 [B, d]: (x [N+1,B,d], dt [B,N], coef [B,N],
+    u [N,B,c] | None, y [B] | None, disc [B] | None); out: existing (x, dt, coef)."""
+    B, d = x0.shape
+    kw = dict(dtype=x0.dtype, device=x0.device)
+    if out is None:
+        out = torch.empty(N + 1, B, d, **kw), torch.empty(B, N, **kw), torch.empty(B, N, **kw)
+    u = torch.empty(N, B, eqp.control_dim, **kw) if want_u else None
+    y, disc = (torch.empty(B, **kw), torch.empty(B, **kw)) if want_cost else (None, None)
+    return (*out, u, y, disc)
 
 
 def rollout_analytic(eqp, scheme: int, x0: torch.Tensor, dw: torch.Tensor | None,
@@ -100,20 +117,9 @@ def rollout_analytic(eqp, scheme: int, x0: torch.Tensor, dw: torch.Tensor | None
     N = num_steps
     if dw is not None and tuple(dw.shape) != (N, B, d):
         raise ValueError(f"dw must be [N, B, d] = {(N, B, d)}, got {tuple(dw.shape)}")
-    kw = dict(dtype=x0.dtype, device=x0.device)
-    if out is None:
-        x = torch.empty(N + 1, B, d, **kw)
-        dt = torch.empty(B, N, **kw)
-        coef = torch.empty(B, N, **kw)
-    else:
-        x, dt, coef = out
-    u = torch.empty(N, B, eqp.control_dim, **kw) if want_u else None
-    y = disc = None
-    if cost_order is not None:
-        y = torch.empty(B, **kw)
-        disc = torch.empty(B, **kw)
+    x, dt, coef, u, y, disc = _rollout_outputs(eqp, x0, N, want_u, cost_order is not None, out)
     call("dpac_rollout_fwd", ctypes.byref(eqp), scheme, _dtype_id(x0), B, N, float(total_time),
-         _ptr(x0.contiguous()), _ptr(dw), seed & 0xFFFFFFFFFFFFFFFF, traj_offset, sample_type,
+         _ptr(x0.contiguous()), _ptr(dw), _u64(seed), traj_offset, sample_type,
          _ptr(x), _ptr(dt), _ptr(coef), _ptr(u), _lib.COST_CRITIC if cost_order is None
          else cost_order, _ptr(y), _ptr(disc), _stream(x0))
     return x, dt, coef, u, y, disc
@@ -321,8 +327,7 @@ def rollout_nn(eqp, scheme: int, x0: torch.Tensor, dw: torch.Tensor, total_time:
     Returns (x [N+1,B,d], dt [B,N], coef [B,N], u [N,B,c] | None, y | None, disc | None,
     saves | None) with saves = (z [N,B,Σ widths[1:]], flag [N,B] int32, disc_t [N,B], mask)
     and mask the hidden activations' sign bits [N,ceil(B/16),mask_tile_bytes] (uint8, dpac.h)
-    where the kernel wrote them
-    (the float 16-row fast path: dpac_rollout_nn_fwd_masked), else None."""
+    where the kernel wrote them (the float 16-row fast path), else None."""
     _require_gpu(x0, dw, *mlp.tensors)
     _check_same(x0, dw, *mlp.tensors)
     B, d = x0.shape
@@ -330,28 +335,17 @@ def rollout_nn(eqp, scheme: int, x0: torch.Tensor, dw: torch.Tensor, total_time:
     if tuple(dw.shape) != (N, B, d):
         raise ValueError(f"dw must be [N, B, d] = {(N, B, d)}, got {tuple(dw.shape)}")
     kw = dict(dtype=x0.dtype, device=x0.device)
-    x = torch.empty(N + 1, B, d, **kw)
-    dt = torch.empty(B, N, **kw)
-    coef = torch.empty(B, N, **kw)
-    u = torch.empty(N, B, eqp.control_dim, **kw) if want_u else None
-    y = disc = None
-    if cost_order is not None:
-        y = torch.empty(B, **kw)
-        disc = torch.empty(B, **kw)
+    x, dt, coef, u, y, disc = _rollout_outputs(eqp, x0, N, want_u, cost_order is not None)
     saves = mask = None
     written = ctypes.c_int32(0)
     if save:
         saves = (torch.empty(N, B, sum(mlp.widths[1:]), **kw),
                  torch.empty(N, B, dtype=torch.int32, device=x0.device), torch.empty(N, B, **kw))
         if MASK_BPTT:  # only where the kernel will write one (16-row fast path)
-            lib = _lib.load()
-            nb = lib.dpac_rollout_nn_mask_bytes(ctypes.byref(mlp.struct), _dtype_id(x0), B, N)
-            if nb < 0:
-                raise _lib.DpacError("dpac_rollout_nn_mask_bytes", int(nb), lib.dpac_last_error().decode())
-            if nb > 0:
-                mb = lib.dpac_rollout_nn_mask_tile_bytes(ctypes.byref(mlp.struct))
+            if _lib.query("dpac_rollout_nn_mask_bytes", ctypes.byref(mlp.struct), _dtype_id(x0), B, N) > 0:
+                mb = _lib.load().dpac_rollout_nn_mask_tile_bytes(ctypes.byref(mlp.struct))
                 mask = torch.empty(N, (B + 15) // 16, mb, dtype=torch.uint8, device=x0.device)
-    call("dpac_rollout_nn_fwd_masked", ctypes.byref(eqp), scheme, _dtype_id(x0), B, N, float(total_time),
+    call("dpac_rollout_nn_fwd", ctypes.byref(eqp), scheme, _dtype_id(x0), B, N, float(total_time),
          ctypes.byref(mlp.struct), _ptr(x0.contiguous()), _ptr(dw.contiguous()), _ptr(x), _ptr(dt),
          _ptr(coef), _ptr(u), _lib.COST_CRITIC if cost_order is None else cost_order, _ptr(y),
          _ptr(disc), _ptr(saves[0] if saves else None), _ptr(saves[1] if saves else None),
@@ -359,6 +353,12 @@ def rollout_nn(eqp, scheme: int, x0: torch.Tensor, dw: torch.Tensor, total_time:
     if saves is not None:
         saves = saves + (mask if written.value else None,)
     return x, dt, coef, u, y, disc, saves
+
+
+def _split_params(params):
+    """(L, gamma[L+2], beta[L+2], W[L+1], b) of DeepNN.trainable_variables()."""
+    L = (len(params) - 1) // 3 - 1
+    return L, params[:L + 2], params[L + 2:2 * L + 4], params[2 * L + 4:3 * L + 5], params[-1]
 
 
 class _ActorRolloutNN(torch.autograd.Function):
@@ -376,8 +376,7 @@ class _ActorRolloutNN(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x0, dw, rs, eqp, scheme, T, N, ekn, *params):
-        L = (len(params) - 1) // 3 - 1
-        gam, bet, Ws, b = params[:L + 2], params[L + 2:2 * L + 4], params[2 * L + 4:3 * L + 5], params[-1]
+        L, gam, bet, Ws, b = _split_params(params)
         view, _, _ = mlp_prepare(gam, bet, Ws, b, ekn, False)
         x, dt, coef, u, y, disc, (z, flag, disc_t, mask) = rollout_nn(
             eqp, scheme, x0, dw, T, N, view, cost_order=_lib.COST_ACTOR, save=True)
@@ -416,8 +415,7 @@ def actor_bptt_grads(eqp, scheme, T, N, ekn, rs, params, saved, g_y, g_disc, g_x
     x, u, dw, z, flag, disc_t = saved[:6]
     mask = saved[6] if len(saved) > 6 else None
     prepared = saved[7] if len(saved) > 7 else None  # the forward's images of the same parameters
-    L = (len(params) - 1) // 3 - 1
-    gam, bet, Ws, b = params[:L + 2], params[L + 2:2 * L + 4], params[2 * L + 4:3 * L + 5], params[-1]
+    L, gam, bet, Ws, b = _split_params(params)
     B, d = x.shape[1], x.shape[2]
     widths = [Ws[0].shape[0]] + [w.shape[1] for w in Ws]
     if prepared is not None and BPTT_MODE == "fused":
@@ -456,7 +454,7 @@ def actor_bptt_grads(eqp, scheme, T, N, ekn, rs, params, saved, g_y, g_disc, g_x
 
 
 # The actor's forward records the hidden activations' sign bits and the BPTT reads them
-# instead of z (dpac_rollout_nn_*_masked; bitwise the same G).  False: z everywhere.
+# instead of z (save_mask of dpac_rollout_nn_fwd / _bwd; bitwise the same G).  False: z everywhere.
 MASK_BPTT = os.environ.get("DPAC_MASK_BPTT", "1") != "0"
 # "fused": the reverse time loop as one dpac_rollout_nn_bwd launch; "loop": the
 # reference implementation of the same loop, dpac_step_bwd + PyTorch per step.
@@ -504,10 +502,8 @@ def mlp_param_grads(view: "MlpView", x, z, G, like, ws_tag: int = 0):
     _require_gpu(x, z, G)
     R = x.shape[0]
     dt = _dtype_id(x)
-    nbytes = _lib.load().dpac_mlp_param_grads_workspace(dt, R, ctypes.byref(view.struct))
-    if nbytes < 0:
-        raise _lib.DpacError("dpac_mlp_param_grads_workspace", nbytes, _lib.load().dpac_last_error().decode())
-    ws = _workspace(int(nbytes), x.device, ws_tag)
+    ws = _workspace(_lib.query("dpac_mlp_param_grads_workspace", dt, R, ctypes.byref(view.struct)),
+                    x.device, ws_tag)
     total = sum(p.numel() for p in like)
     flat = torch.empty(total, dtype=x.dtype, device=x.device)
     if x.stride(1) != 1 or not z.is_contiguous() or not G.is_contiguous():
@@ -536,7 +532,7 @@ def _bptt_fused(eqp, scheme, T, N, L, x, u, dw, z, flag, disc_t, view, wt, wt_km
     B = x.shape[1]
     goff = np.cumsum([0] + widths).tolist()
     Gall = torch.empty(N, B, goff[-1], dtype=x.dtype, device=x.device)
-    _guarded_call(view, "dpac_rollout_nn_bwd_masked", lambda v: (
+    _guarded_call(view, "dpac_rollout_nn_bwd", lambda v: (
         ctypes.byref(eqp), scheme, _dtype_id(x), B, N, float(T), v, _ptr_array(wt), _ptr_array(wt_km),
         _ptr(x), _ptr(u), _ptr(dw), _ptr(z), _ptr(flag), _ptr(disc_t), _ptr(mask), _ptr(g_xN),
         _ptr(g_disc), _ptr(g_y), _ptr(Gall), None, _stream(x)))
@@ -604,45 +600,42 @@ def actor_rollout_nn(eqp, scheme: int, x0, dw, total_time: float, num_steps: int
 ROW_MLP = "kernel"
 
 
-def _split_params(params):
-    L = (len(params) - 1) // 3 - 1
-    return L, params[:L + 2], params[L + 2:2 * L + 4], params[2 * L + 4:3 * L + 5], params[-1]
-
-
-# The row kernels' sign-bit mask (dpac.h dpac_mlp_rows_*_masked, round 5): the split-fp16
+# The row kernels' sign-bit mask (dpac.h save_mask of dpac_mlp_rows_*, round 5): the split-fp16
 # forward records whether each hidden BN output is positive, and the backward chain reads
 # those bits instead of z (bitwise the same G).  DPAC_ROW_MASK=0: z everywhere.
 ROW_MASK = os.environ.get("DPAC_ROW_MASK", "1") != "0"
 
 
-def _row_mask_buffer(view: MlpView, x: torch.Tensor):
-    """The sign-bit mask buffer the masked row forward fills for x's rows, or None where no
-    mask is written (float64, no split-fp16 images)."""
-    nb = _lib.load().dpac_mlp_rows_mask_bytes(ctypes.byref(view.struct), _dtype_id(x), x.shape[0])
-    if nb < 0:
-        raise _lib.DpacError("dpac_mlp_rows_mask_bytes", int(nb), _lib.load().dpac_last_error().decode())
-    return torch.empty(int(nb), dtype=torch.uint8, device=x.device) if nb > 0 else None
+def _rows_fwd(name: str, view: MlpView, x, others, head, out_shape, save: bool, mask: bool):
+    """The body mlp_rows and mlp_rows_td1 share: the checks, the output / z / mask buffers (a
+    mask only where the forward writes one: float, split-fp16 images) and the call
+    name(*head, dtype, R, net, x, ldx, *others, out, z, mask, &written, stream)."""
+    who = name.replace("dpac_", "").replace("_fwd", "")
+    _require_gpu(x, *others, *view.tensors)
+    _check_same(x, *others, *view.tensors)
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError(f"{who}: x must be [rows, d] with unit column stride")
+    R = x.shape[0]
+    out = torch.empty(R, *out_shape, dtype=x.dtype, device=x.device)
+    z = torch.empty(R, sum(view.widths[1:]), dtype=x.dtype, device=x.device) if save else None
+    m = None
+    if save and mask:
+        nb = _lib.query("dpac_mlp_rows_mask_bytes", ctypes.byref(view.struct), _dtype_id(x), R)
+        m = torch.empty(nb, dtype=torch.uint8, device=x.device) if nb > 0 else None
+    written = ctypes.c_int32(0)
+    call(name, *head, _dtype_id(x), R, ctypes.byref(view.struct), ctypes.c_void_p(x.data_ptr()), x.stride(0),
+         *[_ptr(t.contiguous()) for t in others], _ptr(out), _ptr(z), _ptr(m), ctypes.byref(written),
+         _stream(x))
+    if mask:
+        return out, z, (m if written.value else None)
+    return out, z
 
 
 def mlp_rows(view: MlpView, x: torch.Tensor, save: bool = False, mask: bool = False):
     """out [R, w_out] (the network before any Eikonal head) for every row of x [R, d],
     one dpac_mlp_rows_fwd launch; with save=True also z [R, Σ widths[1:]].  With mask=True
     (and save) returns (out, z, sign-bit mask or None where the kernel wrote none)."""
-    _require_gpu(x, *view.tensors)
-    _check_same(x, *view.tensors)
-    if x.dim() != 2 or x.stride(1) != 1:
-        raise ValueError("mlp_rows: x must be [rows, d] with unit column stride")
-    R = x.shape[0]
-    out = torch.empty(R, view.widths[-1], dtype=x.dtype, device=x.device)
-    z = torch.empty(R, sum(view.widths[1:]), dtype=x.dtype, device=x.device) if save else None
-    m = _row_mask_buffer(view, x) if (save and mask) else None
-    written = ctypes.c_int32(0)
-    call("dpac_mlp_rows_fwd_masked", _dtype_id(x), R, ctypes.byref(view.struct),
-         ctypes.c_void_p(x.data_ptr()), x.stride(0), _ptr(out), _ptr(z), _ptr(m), ctypes.byref(written),
-         _stream(x))
-    if mask:
-        return out, z, (m if written.value else None)
-    return out, z
+    return _rows_fwd("dpac_mlp_rows_fwd", view, x, (), (), (view.widths[-1],), save, mask)
 
 
 class _RowMLP(torch.autograd.Function):
@@ -686,7 +679,7 @@ def row_mlp_backward(rs, params, x, z, g_out, want_x: bool, want_params: bool, w
     G = torch.empty(R, sum(view.widths), dtype=x.dtype, device=x.device)
     g_x = torch.empty(R, view.widths[0], dtype=x.dtype, device=x.device) if want_x else None
     g_out = g_out.contiguous()
-    _guarded_call(view, "dpac_mlp_rows_bwd_masked", lambda v: (
+    _guarded_call(view, "dpac_mlp_rows_bwd", lambda v: (
         _dtype_id(x), R, v, _ptr_array(wt), _ptr_array(wt_km), _ptr(z), _ptr(mask), _ptr(g_out), _ptr(G),
         _ptr(g_x), _stream(x)))
     grads = mlp_param_grads(view, x, z, G, params, ws_tag) if want_params else None
@@ -711,23 +704,9 @@ def mlp_rows_td1(eqp, view: MlpView, x: torch.Tensor, u: torch.Tensor, dw: torch
     dpac_mlp_rows_fwd_td1 launch; u [R, c] and dw [R, d] row-aligned with x.  With
     save=True also the backward saves z [R, Σ widths[1:]]; with mask=True (and save)
     returns (gdot, z, sign-bit mask or None) as mlp_rows does."""
-    _require_gpu(x, u, dw, *view.tensors)
-    _check_same(x, u, dw, *view.tensors)
-    if x.dim() != 2 or x.stride(1) != 1:
-        raise ValueError("mlp_rows_td1: x must be [rows, d] with unit column stride")
-    R = x.shape[0]
-    if u.shape[0] != R or dw.shape != (R, eqp.dim):
+    if u.shape[0] != x.shape[0] or dw.shape != (x.shape[0], eqp.dim):
         raise ValueError("mlp_rows_td1: u [R, c] and dw [R, d] must be row-aligned with x")
-    gdot = torch.empty(R, dtype=x.dtype, device=x.device)
-    z = torch.empty(R, sum(view.widths[1:]), dtype=x.dtype, device=x.device) if save else None
-    m = _row_mask_buffer(view, x) if (save and mask) else None
-    written = ctypes.c_int32(0)
-    call("dpac_mlp_rows_fwd_td1_masked", ctypes.byref(eqp), _dtype_id(x), R, ctypes.byref(view.struct),
-         ctypes.c_void_p(x.data_ptr()), x.stride(0), _ptr(u.contiguous()), _ptr(dw.contiguous()),
-         _ptr(gdot), _ptr(z), _ptr(m), ctypes.byref(written), _stream(x))
-    if mask:
-        return gdot, z, (m if written.value else None)
-    return gdot, z
+    return _rows_fwd("dpac_mlp_rows_fwd_td1", view, x, (u, dw), (ctypes.byref(eqp),), (), save, mask)
 
 
 def td_assemble_gdot(eqp, x, u, dt, coef, gdot, *, cost_order: int = _lib.COST_CRITIC):
@@ -780,7 +759,7 @@ def row_mlp_backward_td1(eqp, rs, params, x, z, u, dw, g_gdot, want_params: bool
     R = x.shape[0]
     G = torch.empty(R, sum(view.widths), dtype=x.dtype, device=x.device)
     u, dw, g_gdot = u.contiguous(), dw.contiguous(), g_gdot.contiguous()
-    _guarded_call(view, "dpac_mlp_rows_bwd_td1_masked", lambda v: (
+    _guarded_call(view, "dpac_mlp_rows_bwd_td1", lambda v: (
         ctypes.byref(eqp), _dtype_id(x), R, v, _ptr_array(wt), _ptr_array(wt_km), _ptr(z), _ptr(mask),
         ctypes.c_void_p(x.data_ptr()), x.stride(0), _ptr(u), _ptr(dw), _ptr(g_gdot), _ptr(G), None,
         _stream(x)))
@@ -875,7 +854,7 @@ class _TdAssemble(torch.autograd.Function):
         y = torch.empty(B, dtype=x.dtype, device=x.device)
         disc = torch.empty_like(y)
         call("dpac_td_assemble_fwd", ctypes.byref(eqp), td_type, cost_order, _dtype_id(x), B, N,
-             _ptr(x), _ptr(u), _ptr(dw), seed & 0xFFFFFFFFFFFFFFFF, traj_offset, sample_type,
+             _ptr(x), _ptr(u), _ptr(dw), _u64(seed), traj_offset, sample_type,
              _ptr(dt), _ptr(coef), _ptr(G), _ptr(y), _ptr(disc), _stream(x))
         ctx.save_for_backward(x, u, dw, dt, coef)
         ctx.cfg = (eqp, td_type, seed, traj_offset, sample_type, G is not None)
@@ -891,7 +870,7 @@ class _TdAssemble(torch.autograd.Function):
             B, N = dt.shape
             gG = torch.empty(N, B, eqp.dim, dtype=x.dtype, device=x.device)
             call("dpac_td_assemble_bwd", ctypes.byref(eqp), _dtype_id(x), B, N, _ptr(x),
-                 _ptr(u), _ptr(dw), seed & 0xFFFFFFFFFFFFFFFF, traj_offset, sample_type,
+                 _ptr(u), _ptr(dw), _u64(seed), traj_offset, sample_type,
                  _ptr(dt), _ptr(coef), _ptr(g_y.contiguous()), _ptr(gG), _stream(x))
         return gG, None, None, None, None, None, None, None, None, None, None, None
 
@@ -920,7 +899,7 @@ def td_assemble_bwd(eqp, x, u, dw, dt, coef, g_y, *, seed: int = 0, traj_offset:
     gG = torch.empty(N, B, eqp.dim, dtype=x.dtype, device=x.device)
     call("dpac_td_assemble_bwd", ctypes.byref(eqp), _dtype_id(x), B, N, _ptr(x.contiguous()),
          _ptr(u.contiguous()), _ptr(None if dw is None else dw.contiguous()),
-         seed & 0xFFFFFFFFFFFFFFFF, traj_offset, sample_type, _ptr(dt.contiguous()),
+         _u64(seed), traj_offset, sample_type, _ptr(dt.contiguous()),
          _ptr(coef.contiguous()), _ptr(g_y.contiguous()), _ptr(gG), _stream(x))
     return gG
 
@@ -976,31 +955,37 @@ def v_true(eqp, x):
 _ADAM_ARGS = {}
 
 
-def adam_apply(vs, gs, ms, ss, alpha: float, beta_1: float, beta_2: float, eps: float):
-    """One TF-form Adam step over parameter tensors vs with gradients gs and moments
-    ms, ss (all on the GPU, one dtype): one dpac_adam_apply launch on the current
-    stream.  The pointer arrays are cached per set of addresses (a replayed graph
-    hands back the same gradient buffers every step)."""
-    _require_gpu(*vs, *gs, *ms, *ss)
-    _check_same(vs[0], *vs, *gs, *ms, *ss)
+def _adam_args(who: str, vs, gs, ms, ss):
+    """(n, numel, var, grad, m, v) of the Adam entry points: the C arrays, cached per set of
+    addresses (a replayed graph hands back the same gradient buffers every step)."""
     key = tuple(t.data_ptr() for t in (*vs, *gs, *ms, *ss))
     args = _ADAM_ARGS.get(key)
     if args is None:
         for group in (gs, ms, ss):
+            if len(group) != len(vs):
+                raise ValueError(f"{who}: one gradient and one pair of moments per parameter")
             for v, t in zip(vs, group):
                 if t.shape != v.shape or not t.is_contiguous():
-                    raise ValueError("adam_apply: gradients and moments must match the "
+                    raise ValueError(f"{who}: gradients and moments must match the "
                                      "parameters' shapes and be contiguous")
         if not all(v.is_contiguous() for v in vs):
-            raise ValueError("adam_apply: parameters must be contiguous")
+            raise ValueError(f"{who}: parameters must be contiguous")
         n = len(vs)
         arr = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
         args = (n, (ctypes.c_int64 * n)(*[v.numel() for v in vs]), arr(vs), arr(gs), arr(ms), arr(ss))
         if len(_ADAM_ARGS) > 64:
             _ADAM_ARGS.clear()
         _ADAM_ARGS[key] = args
-    n, numel, pv, pg, pm, ps = args
-    call("dpac_adam_apply", _dtype_id(vs[0]), n, numel, pv, pg, pm, ps, float(alpha),
+    return args
+
+
+def adam_apply(vs, gs, ms, ss, alpha: float, beta_1: float, beta_2: float, eps: float):
+    """One TF-form Adam step over parameter tensors vs with gradients gs and moments
+    ms, ss (all on the GPU, one dtype): one dpac_adam_apply launch on the current
+    stream."""
+    _require_gpu(*vs, *gs, *ms, *ss)
+    _check_same(vs[0], *vs, *gs, *ms, *ss)
+    call("dpac_adam_apply", _dtype_id(vs[0]), *_adam_args("adam_apply", vs, gs, ms, ss), float(alpha),
          float(beta_1), float(beta_2), float(eps), _stream(vs[0]))
 
 
@@ -1014,7 +999,7 @@ def adam_step(vs, gs, ms, ss, state, table, beta_1: float, beta_2: float, eps: f
     t = state[0] + 1 (dpac_adam_step), so the launch can be captured in a HIP graph and follows
     the schedule under replay.  state: adam_state(); table: the 1-D device array of alphas in the
     variables' dtype (solver.adam_alpha_table).  advance: state[0] += 1 once the whole call has
-    read it; with empty lists only that.  Pointer arrays cached as adam_apply's."""
+    read it; with empty lists only that."""
     _require_gpu(state, table, *vs, *gs, *ms, *ss)
     _check_same(table, *vs, *gs, *ms, *ss)
     if (state.dtype != torch.int64 or state.numel() < 2 or state.device != table.device
@@ -1022,24 +1007,6 @@ def adam_step(vs, gs, ms, ss, state, table, beta_1: float, beta_2: float, eps: f
         raise ValueError("adam_step: state must be ops.adam_state() on the table's device")
     if table.dim() != 1 or table.numel() < 1 or not table.is_contiguous():
         raise ValueError("adam_step: table must be a contiguous 1-D tensor with at least one entry")
-    key = tuple(t.data_ptr() for t in (*vs, *gs, *ms, *ss))
-    args = _ADAM_ARGS.get(key)
-    if args is None:
-        for group in (gs, ms, ss):
-            if len(group) != len(vs):
-                raise ValueError("adam_step: one gradient and one pair of moments per parameter")
-            for v, t in zip(vs, group):
-                if t.shape != v.shape or not t.is_contiguous():
-                    raise ValueError("adam_step: gradients and moments must match the "
-                                     "parameters' shapes and be contiguous")
-        if not all(v.is_contiguous() for v in vs):
-            raise ValueError("adam_step: parameters must be contiguous")
-        n = len(vs)
-        arr = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
-        args = (n, (ctypes.c_int64 * n)(*[v.numel() for v in vs]), arr(vs), arr(gs), arr(ms), arr(ss))
-        if len(_ADAM_ARGS) > 64:
-            _ADAM_ARGS.clear()
-        _ADAM_ARGS[key] = args
-    n, numel, pv, pg, pm, ps = args
-    call("dpac_adam_step", _dtype_id(table), n, numel, pv, pg, pm, ps, state.data_ptr(), table.data_ptr(),
-         table.numel(), float(beta_1), float(beta_2), float(eps), 1 if advance else 0, _stream(table))
+    call("dpac_adam_step", _dtype_id(table), *_adam_args("adam_step", vs, gs, ms, ss), state.data_ptr(),
+         table.data_ptr(), table.numel(), float(beta_1), float(beta_2), float(eps), 1 if advance else 0,
+         _stream(table))

@@ -52,13 +52,15 @@ extern "C" {
 /* 2: dpac_rollout_nn_bwd / dpac_mlp_rows_bwd take weight_t_km (round 2); adds
  * dpac_rollout_nn_mask_bytes.  3: dpac_mlp gains weight_x3 / weight_t_x3 (split-fp16
  * images) and dpac_mlp_prepare writes them.  4: the split-fp16 images are fragment-major
- * (below) and the float fused rollout / BPTT (dpac_rollout_nn_fwd[_masked],
- * dpac_rollout_nn_bwd_masked) read them too.  5: adds dpac_critic_loss_grad.  6: dpac_mlp gains
- * `status` (the split-fp16 range guard, below).  7: adds the row kernels' sign-bit mask
- * (dpac_mlp_rows_mask_bytes, dpac_mlp_rows_{fwd,bwd}[_td1]_masked).  8: dpac_mlp gains
- * `guard_phase` (the range guard's fallback launched apart from its split-fp16 launch, below).
+ * (below) and the float fused rollout / BPTT (dpac_rollout_nn_fwd / _bwd) read them too.
+ * 5: adds dpac_critic_loss_grad.  6: dpac_mlp gains `status` (the split-fp16 range guard,
+ * below).  7: adds the row kernels' sign-bit mask (dpac_mlp_rows_mask_bytes and _masked twins of
+ * dpac_mlp_rows_{fwd,bwd}[_td1]).  8: dpac_mlp gains `guard_phase` (the range guard's fallback
+ * launched apart from its split-fp16 launch, below).  9: adds dpac_adam_step.
+ * 10: one name per entry point: the six _masked twins take over their base names, the mask
+ * arguments optional (NULL); the short signatures are gone.
  * Bindings must refuse a library of another version. */
-#define DPAC_ABI_VERSION 9
+#define DPAC_ABI_VERSION 10
 
 /* status codes besides hipError_t values */
 #define DPAC_OK 0
@@ -301,7 +303,17 @@ int dpac_actor_cost_fwd(const dpac_eqn_params* eq, int32_t dtype,
  * Backward saves (optional, all or none): save_z [N][B][Σ_{i>=1} width[i]] the
  * pre-BN output of every dense layer (layer i at column offset
  * Σ_{1<=k<i} width[k]), save_flag [N][B] and save_disc [N][B] the flag and the
- * discount entering step t. */
+ * discount entering step t.
+ * Sign-bit mask (optional, with the backward saves): the BPTT needs of the saved pre-BN outputs
+ * z only whether each hidden BN output was positive (the activation factor 1 + [y > 0]); the
+ * forward records those bits as it computes them, save_mask
+ * [N][ceil(B / 16)][dpac_rollout_nn_mask_tile_bytes(actor)] bytes (per 16-row tile: row r of
+ * hidden layer l, column c at bit r % 4 of byte 13*64 l + 64 (c / 16) + 16 (r / 4) + c % 16, the
+ * MFMA accumulator's lane layout), and dpac_rollout_nn_bwd reads them instead of z (z is still
+ * needed by the parameter gradients and the Eikonal head).  The mask is written only on the
+ * float 16-row fast path (hidden layers 193..208 wide, d and out <= 32, k-major images, batches
+ * > 1024 or DPAC_NN_TILE=16): *mask_written (host, optional; zeroed on entry) reports whether
+ * it was; pass the mask to the backward only then.  Results are bitwise those without a mask. */
 #define DPAC_MLP_MAX_HIDDEN 4
 #define DPAC_MLP_MAX_WIDTH 256
 typedef struct dpac_mlp {
@@ -323,16 +335,25 @@ typedef struct dpac_mlp {
 #define DPAC_GUARD_SPLIT_ONLY 1
 #define DPAC_GUARD_FALLBACK_ONLY 2
 
+/* save_mask bytes per 16-row tile and step (0 on a bad argument) */
+int32_t dpac_rollout_nn_mask_tile_bytes(const dpac_mlp* actor);
+/* The save_mask bytes dpac_rollout_nn_fwd writes for this call
+ * (N * ceil(B / 16) * dpac_rollout_nn_mask_tile_bytes), or 0 where it writes none (float64,
+ * 4-row tiles at B <= 1024, no fast path): allocate the mask only when this is > 0.
+ * -1 on a bad argument. */
+int64_t dpac_rollout_nn_mask_bytes(const dpac_mlp* actor, int32_t dtype, int64_t num_sample,
+                                   int32_t num_steps);
 int dpac_rollout_nn_fwd(const dpac_eqn_params* eq, int32_t scheme, int32_t dtype,
                         int64_t num_sample, int32_t num_steps, double total_time,
                         const dpac_mlp* actor, const void* x0, const void* dw, void* x,
                         void* dt, void* coef, void* u, int32_t cost_order, void* y,
                         void* disc, void* save_z, int32_t* save_flag, void* save_disc,
-                        void* stream);
+                        uint8_t* save_mask, int32_t* mask_written, void* stream);
 
 /* The actor's BPTT through a dpac_rollout_nn_fwd rollout (what GradientTape does
  * for solver.py:92-97), as one launch.  Inputs: the forward's x, u, dw and its
- * saves; `weight_t[i]` = (weight[i] * bn_scale[i+1])^T, [width[i+1]][width[i]]
+ * saves (save_mask: the forward's sign bits where it wrote them, else NULL);
+ * `weight_t[i]` = (weight[i] * bn_scale[i+1])^T, [width[i+1]][width[i]]
  * row-major, i = 0..n_hidden; weight_t_km (optional, float only, NULL = not used)
  * their k-major images, [width[i]][roundup(width[i+1], 16)] (dpac_mlp_prepare's
  * weight_t_km output); the upstream gradients g_xN [B][d] (dL/dx_N),
@@ -347,42 +368,10 @@ int dpac_rollout_nn_bwd(const dpac_eqn_params* eq, int32_t scheme, int32_t dtype
                         const dpac_mlp* actor, const void* const* weight_t,
                         const void* const* weight_t_km, const void* x,
                         const void* u, const void* dw, const void* save_z,
-                        const int32_t* save_flag, const void* save_disc, const void* g_xN,
-                        const void* g_disc, const void* g_y, void* G, void* g_x0, void* stream);
-
-/* The same forward / BPTT pair with a sign-bit mask: the BPTT needs of the saved pre-BN
- * outputs z only whether each hidden BN output was positive (the activation factor
- * 1 + [y > 0]); dpac_rollout_nn_fwd_masked records those bits as the forward computes
- * them, save_mask [N][ceil(B / 16)][dpac_rollout_nn_mask_tile_bytes(actor)] bytes (per
- * 16-row tile: row r of hidden layer l, column c at bit r % 4 of byte
- * 13*64 l + 64 (c / 16) + 16 (r / 4) + c % 16, the MFMA accumulator's lane layout), and
- * dpac_rollout_nn_bwd_masked reads them instead of z (z is still needed by the parameter
- * gradients and the Eikonal head).  The mask is written only on the float 16-row fast path
- * (hidden layers 193..208 wide, d and out <= 32, k-major images, batches > 1024 or
- * DPAC_NN_TILE=16): *mask_written (host) reports whether it was; pass it to the backward only
- * then.  Results are bitwise those of the unmasked pair. */
-int32_t dpac_rollout_nn_mask_tile_bytes(const dpac_mlp* actor);
-/* The save_mask bytes dpac_rollout_nn_fwd_masked writes for this call
- * (N * ceil(B / 16) * dpac_rollout_nn_mask_tile_bytes), or 0 where it writes none (float64,
- * 4-row tiles at B <= 1024, no fast path): allocate the mask only when this is > 0.
- * -1 on a bad argument. */
-int64_t dpac_rollout_nn_mask_bytes(const dpac_mlp* actor, int32_t dtype, int64_t num_sample,
-                                   int32_t num_steps);
-int dpac_rollout_nn_fwd_masked(const dpac_eqn_params* eq, int32_t scheme, int32_t dtype,
-                               int64_t num_sample, int32_t num_steps, double total_time,
-                               const dpac_mlp* actor, const void* x0, const void* dw, void* x,
-                               void* dt, void* coef, void* u, int32_t cost_order, void* y,
-                               void* disc, void* save_z, int32_t* save_flag, void* save_disc,
-                               uint8_t* save_mask, int32_t* mask_written, void* stream);
-int dpac_rollout_nn_bwd_masked(const dpac_eqn_params* eq, int32_t scheme, int32_t dtype,
-                               int64_t num_sample, int32_t num_steps, double total_time,
-                               const dpac_mlp* actor, const void* const* weight_t,
-                               const void* const* weight_t_km, const void* x,
-                               const void* u, const void* dw, const void* save_z,
-                               const int32_t* save_flag, const void* save_disc,
-                               const uint8_t* save_mask, const void* g_xN,
-                               const void* g_disc, const void* g_y, void* G, void* g_x0,
-                               void* stream);
+                        const int32_t* save_flag, const void* save_disc,
+                        const uint8_t* save_mask, const void* g_xN,
+                        const void* g_disc, const void* g_y, void* G, void* g_x0,
+                        void* stream);
 
 /* ---- a dpac_mlp over independent rows (the critic's networks) -------------
  * Forward: out [rows][width[n_hidden+1]] = the network (bn_0 -> (dense -> bn ->
@@ -396,12 +385,15 @@ int dpac_rollout_nn_bwd_masked(const dpac_eqn_params* eq, int32_t scheme, int32_
  * save_z, writes G [rows][Σ_i width[i]], block i = dL/d(output of BN_i) — the
  * input of dpac_mlp_param_grads — and optionally g_x [rows][width[0]] = dL/dx.
  * weight_t[i] = (weight[i] * bn_scale[i+1])^T, [width[i+1]][width[i]] row-major;
- * weight_t_km (optional, float only) their k-major images, as for dpac_rollout_nn_bwd. */
+ * weight_t_km (optional, float only) their k-major images, as for dpac_rollout_nn_bwd.
+ * save_mask / mask_written (optional): the sign-bit mask, below. */
 int dpac_mlp_rows_fwd(int32_t dtype, int64_t rows, const dpac_mlp* net, const void* x,
-                      int64_t ldx, void* out, void* save_z, void* stream);
-int dpac_mlp_rows_bwd(int32_t dtype, int64_t rows, const dpac_mlp* net, const void* const* weight_t,
-                      const void* const* weight_t_km, const void* save_z, const void* g_out, void* G,
-                      void* g_x, void* stream);
+                      int64_t ldx, void* out, void* save_z, uint8_t* save_mask,
+                      int32_t* mask_written, void* stream);
+int dpac_mlp_rows_bwd(int32_t dtype, int64_t rows, const dpac_mlp* net,
+                      const void* const* weight_t, const void* const* weight_t_km,
+                      const void* save_z, const uint8_t* save_mask, const void* g_out,
+                      void* G, void* g_x, void* stream);
 
 /* ---- the G network with the TD1 dot fused ---------
  * solver.py:179-184 evaluates G = NN_value_grad(x_t) and immediately dots it with
@@ -413,17 +405,19 @@ int dpac_mlp_rows_bwd(int32_t dtype, int64_t rows, const dpac_mlp* net, const vo
  * dot dpac_td_assemble_fwd(DPAC_TD1) forms from the same G.
  * dpac_mlp_rows_bwd_td1 is dpac_mlp_rows_bwd with dL/d out = g_gdot[r]·(σ dw)_r,
  * formed in its prologue (bitwise dpac_td_assemble_bwd's d y / d G times the same
- * upstream gradient). */
+ * upstream gradient).  save_mask / mask_written (optional): the sign-bit mask, below. */
 int dpac_mlp_rows_fwd_td1(const dpac_eqn_params* eq, int32_t dtype, int64_t rows,
                           const dpac_mlp* net, const void* x, int64_t ldx, const void* u,
-                          const void* dw, void* gdot, void* save_z, void* stream);
+                          const void* dw, void* gdot, void* save_z, uint8_t* save_mask,
+                          int32_t* mask_written, void* stream);
 int dpac_mlp_rows_bwd_td1(const dpac_eqn_params* eq, int32_t dtype, int64_t rows,
                           const dpac_mlp* net, const void* const* weight_t,
-                          const void* const* weight_t_km, const void* save_z, const void* x,
-                          int64_t ldx, const void* u, const void* dw, const void* g_gdot,
-                          void* G, void* g_x, void* stream);
+                          const void* const* weight_t_km, const void* save_z,
+                          const uint8_t* save_mask, const void* x, int64_t ldx,
+                          const void* u, const void* dw, const void* g_gdot, void* G,
+                          void* g_x, void* stream);
 
-/* The row kernels with a sign-bit mask (round 5, ABI 7).  The backward chain needs of the
+/* The row kernels' sign-bit mask (round 5, ABI 7).  The backward chain needs of the
  * forward's saved z only whether each hidden BN output was positive (the activation factor
  * 1 + [y > 0], solver.py:269); the split-fp16 forward records those bits as it computes them,
  * save_mask = dpac_mlp_rows_mask_bytes bytes of 32-bit words: per hidden layer h = 1..n_hidden
@@ -431,31 +425,14 @@ int dpac_mlp_rows_bwd_td1(const dpac_eqn_params* eq, int32_t dtype, int64_t rows
  * ((h - 1) nblk + b) * 512 + 64 w + 16 q + r (w < 8, q < 4, r < 16) holds at bit 4 (2 t + j) + e
  * (t, e < 4; j < 2) whether BN_h's output of row 64 b + 16 t + r, feature 16 (w + 8 j) + 4 q + e,
  * is > 0 (0 past width[h] and past the last row) — the split-fp16 kernels' accumulator layout,
- * so each lane writes and reads one word per layer.  The masked backward reads them instead of z (z is
- * still required: the parameter gradients and the exact-f32 fallback read it).  The mask is
+ * so each lane writes and reads one word per layer.  A backward given save_mask reads them instead
+ * of z (z is still required: the parameter gradients and the exact-f32 fallback read it).  The mask is
  * written only by the float split-fp16 forward (every weight_x3 given) and only with save_z:
- * *mask_written (host, optional) reports whether it was; pass it to the backward only then.
- * Results are bitwise those of the unmasked entry points (tests/test_gpu_mlp.py).
+ * *mask_written (host, optional; zeroed on entry) reports whether it was; pass the mask to the
+ * backward only then.  Results are bitwise those without a mask (tests/test_gpu_mlp.py).
  * dpac_mlp_rows_mask_bytes: the bytes for `rows` rows, 0 where no mask is written (float64,
  * no split-fp16 images), -1 on a bad argument. */
 int64_t dpac_mlp_rows_mask_bytes(const dpac_mlp* net, int32_t dtype, int64_t rows);
-int dpac_mlp_rows_fwd_masked(int32_t dtype, int64_t rows, const dpac_mlp* net, const void* x,
-                             int64_t ldx, void* out, void* save_z, uint8_t* save_mask,
-                             int32_t* mask_written, void* stream);
-int dpac_mlp_rows_bwd_masked(int32_t dtype, int64_t rows, const dpac_mlp* net,
-                             const void* const* weight_t, const void* const* weight_t_km,
-                             const void* save_z, const uint8_t* save_mask, const void* g_out,
-                             void* G, void* g_x, void* stream);
-int dpac_mlp_rows_fwd_td1_masked(const dpac_eqn_params* eq, int32_t dtype, int64_t rows,
-                                 const dpac_mlp* net, const void* x, int64_t ldx, const void* u,
-                                 const void* dw, void* gdot, void* save_z, uint8_t* save_mask,
-                                 int32_t* mask_written, void* stream);
-int dpac_mlp_rows_bwd_td1_masked(const dpac_eqn_params* eq, int32_t dtype, int64_t rows,
-                                 const dpac_mlp* net, const void* const* weight_t,
-                                 const void* const* weight_t_km, const void* save_z,
-                                 const uint8_t* save_mask, const void* x, int64_t ldx,
-                                 const void* u, const void* dw, const void* g_gdot, void* G,
-                                 void* g_x, void* stream);
 
 /* ---- parameter gradients of a dpac_mlp over independent rows -------------
  * What GradientTape returns for DeepNN's trainable variables (solver.py:88,95

@@ -115,7 +115,7 @@ int main(void) {
                            DPAC_COST_ACTOR, P, (int32_t*)P, P, P, NULL, NULL, NULL), "step_fwd: u NULL");
   expect_err(dpac_step_bwd(&e, DPAC_SCHEME_ADAPTIVE, DPAC_F32, 16, 10, 0.2, P, P, P, (int32_t*)P, P,
                            DPAC_COST_ACTOR, NULL, NULL, NULL, P, P, NULL, NULL), "step_bwd: g_x_out NULL");
-  expect_err(dpac_td_assemble_fwd(&e, 3, DPAC_COST_CRITIC, DPAC_F32, 16, 10, P, P, P, 1, 0, 0, P, P, P, P, P,
+  expect_err(dpac_td_assemble_fwd(&e, 9, DPAC_COST_CRITIC, DPAC_F32, 16, 10, P, P, P, 1, 0, 0, P, P, P, P, P,
                                   NULL), "td_fwd: bad td_type");
   expect_err(dpac_td_assemble_fwd(&e, DPAC_TD1, DPAC_COST_CRITIC, DPAC_F32, 16, 10, P, P, P, 1, 0, 0, P, P, NULL,
                                   P, P, NULL), "td_fwd: TD1 without G");
@@ -129,37 +129,61 @@ int main(void) {
   dpac_mlp m;
   memset(&m, 0, sizeof m);
   expect_err(dpac_rollout_nn_fwd(&e, DPAC_SCHEME_ADAPTIVE, DPAC_F32, 16, 10, 0.2, NULL, P, P, P, P, P, P,
-                                 DPAC_COST_ACTOR, NULL, NULL, NULL, NULL, NULL, NULL), "rollout_nn: NULL mlp");
+                                 DPAC_COST_ACTOR, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL), "rollout_nn: NULL mlp");
   m.n_hidden = 9;
   expect_err(dpac_rollout_nn_fwd(&e, DPAC_SCHEME_ADAPTIVE, DPAC_F32, 16, 10, 0.2, &m, P, P, P, P, P, P,
-                                 DPAC_COST_ACTOR, NULL, NULL, NULL, NULL, NULL, NULL), "rollout_nn: n_hidden 9");
+                                 DPAC_COST_ACTOR, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL), "rollout_nn: n_hidden 9");
   m.n_hidden = 2;
   m.width[0] = 20; m.width[1] = 300; m.width[2] = 64; m.width[3] = 20;
   expect_err(dpac_rollout_nn_fwd(&e, DPAC_SCHEME_ADAPTIVE, DPAC_F32, 16, 10, 0.2, &m, P, P, P, P, P, P,
-                                 DPAC_COST_ACTOR, NULL, NULL, NULL, NULL, NULL, NULL), "rollout_nn: width 300");
+                                 DPAC_COST_ACTOR, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL), "rollout_nn: width 300");
   m.width[1] = 64;
   for (int i = 0; i < 4; ++i) m.bn_scale[i] = m.bn_shift[i] = P;
   for (int i = 0; i < 3; ++i) m.weight[i] = P;
   expect_err(dpac_rollout_nn_fwd(&e, DPAC_SCHEME_ADAPTIVE, DPAC_F32, 16, 10, 0.2, &m, P, P, P, P, P, P,
-                                 DPAC_COST_ACTOR, NULL, NULL, NULL, NULL, NULL, NULL), "rollout_nn: bias NULL");
+                                 DPAC_COST_ACTOR, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL), "rollout_nn: bias NULL");
   m.bias = P;
   m.ekn_head = 1;
   expect_err(dpac_rollout_nn_fwd(&e, DPAC_SCHEME_ADAPTIVE, DPAC_F32, 16, 10, 0.2, &m, P, P, P, P, P, P,
-                                 DPAC_COST_ACTOR, NULL, NULL, NULL, NULL, NULL, NULL), "rollout_nn: ekn head on LQR");
+                                 DPAC_COST_ACTOR, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL), "rollout_nn: ekn head on LQR");
   m.ekn_head = 0;
   expect_err(dpac_rollout_nn_fwd(&e, DPAC_SCHEME_ADAPTIVE, DPAC_F32, 16, 10, 0.2, &m, P, P, P, P, P, P,
-                                 DPAC_COST_ACTOR, NULL, NULL, P, NULL, NULL, NULL), "rollout_nn: partial saves");
+                                 DPAC_COST_ACTOR, NULL, NULL, P, NULL, NULL, NULL, NULL, NULL), "rollout_nn: partial saves");
   m.width[0] = 19;
   expect_err(dpac_rollout_nn_fwd(&e, DPAC_SCHEME_ADAPTIVE, DPAC_F32, 16, 10, 0.2, &m, P, P, P, P, P, P,
-                                 DPAC_COST_ACTOR, NULL, NULL, NULL, NULL, NULL, NULL), "rollout_nn: width[0] != dim");
+                                 DPAC_COST_ACTOR, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL), "rollout_nn: width[0] != dim");
   m.width[0] = 20;
   const void* wt3[3] = {P, NULL, P};
   expect_err(dpac_rollout_nn_bwd(&e, DPAC_SCHEME_ADAPTIVE, DPAC_F32, 16, 10, 0.2, &m, wt3, NULL, P, P, P, P,
-                                 (int32_t*)P, P, NULL, NULL, P, P, NULL, NULL), "rollout_nn_bwd: weight_t[1] NULL");
-  expect_err(dpac_mlp_rows_fwd(DPAC_F32, 0, &m, P, 20, P, NULL, NULL), "rows_fwd: rows = 0");
-  expect_err(dpac_mlp_rows_fwd(DPAC_F32, 16, &m, P, 5, P, NULL, NULL), "rows_fwd: ldx < width[0]");
-  expect_err(dpac_mlp_rows_bwd(7, 16, &m, wt3, NULL, P, P, P, NULL, NULL), "rows_bwd: bad dtype");
-  expect_err(dpac_mlp_rows_bwd(DPAC_F32, 16, &m, wt3, NULL, P, P, P, NULL, NULL), "rows_bwd: weight_t[1] NULL");
+                                 (int32_t*)P, P, NULL, NULL, NULL, P, P, NULL, NULL), "rollout_nn_bwd: weight_t[1] NULL");
+  expect_err(dpac_mlp_rows_fwd(DPAC_F32, 0, &m, P, 20, P, NULL, NULL, NULL, NULL), "rows_fwd: rows = 0");
+  expect_err(dpac_mlp_rows_fwd(DPAC_F32, 16, &m, P, 5, P, NULL, NULL, NULL, NULL), "rows_fwd: ldx < width[0]");
+  expect_err(dpac_mlp_rows_bwd(7, 16, &m, wt3, NULL, P, NULL, P, P, NULL, NULL), "rows_bwd: bad dtype");
+  expect_err(dpac_mlp_rows_bwd(DPAC_F32, 16, &m, wt3, NULL, P, NULL, P, P, NULL, NULL),
+             "rows_bwd: weight_t[1] NULL");
+  /* the sign-bit mask arguments: a mask needs the saves it stands in for, and a failed call
+   * leaves *mask_written = 0 */
+  int32_t written = 1;
+  expect_err(dpac_mlp_rows_fwd(DPAC_F32, 16, &m, P, 20, P, NULL, (uint8_t*)P, &written, NULL),
+             "rows_fwd: save_mask without save_z");
+  written = 1;
+  expect_err(dpac_rollout_nn_fwd(&e, DPAC_SCHEME_ADAPTIVE, DPAC_F32, 16, 10, 0.2, &m, P, P, P, P, P, P,
+                                 DPAC_COST_ACTOR, NULL, NULL, NULL, NULL, NULL, (uint8_t*)P, &written, NULL),
+             "rollout_nn: save_mask without the saves");
+  ++checks;
+  if (written != 0) {
+    printf("FAIL rollout_nn: *mask_written must be 0 after a failed call\n");
+    ++fails;
+  }
+  /* the fused TD1 pair: the G network is d wide at both ends (m: 20 -> 64 -> 64 -> 20) */
+  expect_err(dpac_mlp_rows_fwd_td1(&e, DPAC_F32, 16, &m, P, 20, P, P, P, NULL, (uint8_t*)P, NULL, NULL),
+             "rows_fwd_td1: save_mask without save_z");
+  m.width[3] = 16;
+  expect_err(dpac_mlp_rows_fwd_td1(&e, DPAC_F32, 16, &m, P, 20, P, P, P, NULL, NULL, NULL, NULL),
+             "rows_fwd_td1: output width != dim");
+  m.width[3] = 20;
+  expect_err(dpac_mlp_rows_bwd_td1(&e, DPAC_F32, 16, &m, wt3, NULL, P, NULL, P, 20, P, P, P, P, NULL, NULL),
+             "rows_bwd_td1: weight_t[1] NULL");
   ++checks;
   if (dpac_mlp_param_grads_workspace(DPAC_F32, -1, &m) != -1) {
     printf("FAIL param_grads_workspace: rows < 0 must give -1\n");
@@ -177,6 +201,15 @@ int main(void) {
              "adam: n_tensors < 0");
   expect_err(dpac_adam_apply(DPAC_F32, 2, NULL, vars, grads, vars, vars, 1e-3, 0.9, 0.999, 1e-8, NULL),
              "adam: numel NULL");
+  dpac_adam_state* st = (dpac_adam_state*)P;
+  int64_t one[1] = {10};
+  expect_err(dpac_adam_step(DPAC_F32, 1, one, vars, grads, vars, vars, st, P, 0, 0.9, 0.999, 1e-8, 1, NULL),
+             "adam_step: table_len = 0");
+  expect_err(dpac_adam_step(DPAC_F32, 1, one, vars, grads, vars, vars, NULL, P, 8, 0.9, 0.999, 1e-8, 1, NULL),
+             "adam_step: state NULL");
+  expect_err(dpac_adam_step(DPAC_F32, 2, numel, vars, grads, vars, vars, st, P, 8, 0.9, 0.999, 1e-8, 1, NULL),
+             "adam_step: negative numel");
+  expect_err(dpac_critic_loss_grad(DPAC_F32, 16, P, P, P, P, 1.0, 0.0, P, P, NULL), "critic_loss_grad: delta_clip = 0");
 
   printf("%d checks, %d failed\n", checks, fails);
   return fails ? 1 : 0;

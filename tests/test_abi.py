@@ -128,11 +128,11 @@ def test_validation_without_gpu():
         ("dpac_equation_eval", (ctypes.byref(p), 99, 0, 16, dummy, dummy, dummy, None), "eval"),
         # fused TD1: the G network's widths must be d
         ("dpac_mlp_rows_fwd_td1", (ctypes.byref(p), 0, 64, ctypes.byref(_net(20, 16)), dummy, 20, dummy,
-                                   dummy, dummy, None, None), "output width"),
+                                   dummy, dummy, None, None, None, None), "output width"),
         ("dpac_mlp_rows_fwd_td1", (ctypes.byref(p), 0, 64, ctypes.byref(_net(20, 20)), dummy, 20, dummy,
-                                   dummy, None, None, None), "gdot"),
+                                   dummy, None, None, None, None, None), "gdot"),
         ("dpac_mlp_rows_bwd_td1", (ctypes.byref(p), 0, 64, ctypes.byref(_net(20, 20)), None, None, dummy,
-                                   dummy, 20, dummy, dummy, dummy, dummy, None, None), "weight_t"),
+                                   None, dummy, 20, dummy, dummy, dummy, dummy, None, None), "weight_t"),
         ("dpac_td_assemble_bwd_gdot", (ctypes.byref(p), 0, 16, 10, dummy, dummy, None, dummy, None),
          "g_y"),
         ("dpac_td_assemble_fwd", (ctypes.byref(p), _lib.TD1_GDOT, 0, 0, 16, 10, dummy, dummy, None, 0, 0,
@@ -163,11 +163,11 @@ def test_fused_td1_rejects_eikonal_head():
     net.ekn_head = 1
     with pytest.raises(_lib.DpacError) as ei:
         _lib.call("dpac_mlp_rows_fwd_td1", ctypes.byref(p), 0, 64, ctypes.byref(net), d, 20, d, d, d,
-                  None, None)
+                  None, None, None, None)
     assert ei.value.code == _lib.DPAC_EINVAL and "eikonal" in str(ei.value).lower()
     with pytest.raises(_lib.DpacError) as ei:
         _lib.call("dpac_mlp_rows_bwd_td1", ctypes.byref(p), 0, 64, ctypes.byref(net), (ctypes.c_void_p * 2)(d, d),
-                  None, d, d, 20, d, d, d, d, None, None)
+                  None, d, None, d, 20, d, d, d, d, None, None)
     assert ei.value.code == _lib.DPAC_EINVAL
 
 

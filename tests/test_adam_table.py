@@ -83,4 +83,4 @@ def test_adam_step_validation_without_gpu():
             _lib.call("dpac_adam_step", _lib.F32, args[0], args[1], args[2], arr, arr, arr, d, d, 8,
                       0.9, 0.999, 1e-8, 0, None)
         assert ei.value.code == _lib.DPAC_EINVAL
-    assert _lib.ABI_VERSION == 9 == _lib.load().dpac_abi_version()
+    assert _lib.ABI_VERSION == 10 == _lib.load().dpac_abi_version()

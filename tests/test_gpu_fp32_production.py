@@ -6,7 +6,7 @@ The production float32 path differs from the float64 one in code, not only in pr
     193..208-wide hidden layers), whose products run on split-fp16 MFMA (dpac_rollout_nn_x3.h:
     three v_mfma_f32_16x16x32_f16 per 32-k step, f32 accumulate), as do the critic's V / G row
     kernels (dpac_mlp_x3.h) and every network's parameter gradients (dpac_mlp_grad_x3.h);
-  * the BPTT reading the forward's activation sign bits (dpac_rollout_nn_*_masked);
+  * the BPTT reading the forward's activation sign bits (save_mask of dpac_rollout_nn_fwd / _bwd);
   * the k-major weight images (dwordx4 B loads);
   * the critic's G network with the TD1 dot fused (dpac_mlp_rows_fwd_td1), HIP graphs and the
     split critic / actor steps on side streams.

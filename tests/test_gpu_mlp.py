@@ -404,10 +404,10 @@ def test_row_mlp_stacked_input_and_errors():
     lib = _lib.load()
     view = net.mlp_view()
     assert lib.dpac_mlp_rows_fwd(_lib.F64, 10, ctypes.byref(view.struct), None, 5, None, None,
-                                 None) == _lib.DPAC_EINVAL
+                                 None, None, None) == _lib.DPAC_EINVAL
     assert lib.dpac_mlp_rows_fwd(_lib.F64, 10, ctypes.byref(view.struct),
                                  ctypes.c_void_p(x.data_ptr()), 3, ctypes.c_void_p(x.data_ptr()),
-                                 None, None) == _lib.DPAC_EINVAL  # ldx < d
+                                 None, None, None, None) == _lib.DPAC_EINVAL  # ldx < d
 
 
 @pytest.mark.parametrize("hidden,R", [((200, 200, 200), 20000), ((200, 200, 200), 777), ((52, 100, 36), 1234),
@@ -415,8 +415,8 @@ def test_row_mlp_stacked_input_and_errors():
 @pytest.mark.parametrize("td1", [False, True])
 def test_row_backward_sign_mask_bitwise(hidden, R, td1, monkeypatch):
     """Round 5: the split-fp16 row forward records the hidden BN outputs'
-    sign bits (dpac_mlp_rows_fwd[_td1]_masked) and the backward chain reads them instead of z
-    (dpac_mlp_rows_bwd[_td1]_masked).  The mask's bits equal [shift_h + z_h * scale_h > 0]
+    sign bits (save_mask of dpac_mlp_rows_fwd[_td1]) and the backward chain reads them instead of z
+    (save_mask of dpac_mlp_rows_bwd[_td1]).  The mask's bits equal [shift_h + z_h * scale_h > 0]
     formed from the saved z (f32, the kernels' expression), and the masked backward's G,
     dL/dx and parameter gradients equal the z-reading backward's bit for bit (ragged row
     counts, widths that are not multiples of 4 or 16, the TD1 prologue)."""

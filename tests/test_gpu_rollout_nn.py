@@ -414,11 +414,11 @@ def test_actor_fast_path_bitwise(name, d, hidden, B, scheme):
     ("LQR", 4, (208, 200, 193), 20, "adaptive"),
     ("LQR_var", 20, (200,), 17, "naive")])
 def test_bptt_sign_mask_bitwise(name, d, hidden, B, scheme, monkeypatch):
-    """The actor forward's sign-bit mask (dpac_rollout_nn_fwd_masked: bit r % 4 of byte
+    """The actor forward's sign-bit mask (save_mask of dpac_rollout_nn_fwd: bit r % 4 of byte
     [13 l + c/16][r/4 % 4][c % 16] of row r's 16-row tile = [BN_{l+1}(z) > 0] of hidden layer
     l) leaves every forward output
     bitwise unchanged, matches the signs recomputed from the saved z, and the BPTT reading
-    it (dpac_rollout_nn_bwd_masked) gives bitwise the G of the z-based BPTT."""
+    it (dpac_rollout_nn_bwd) gives bitwise the G of the z-based BPTT."""
     N, T = 12, 0.2
     cfg = full_config(name, d, N=N, hidden=hidden, scheme=scheme, dtype="float32")
     ep = getattr(peq, name)(cfg.eqn_config)

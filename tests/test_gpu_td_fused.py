@@ -119,7 +119,7 @@ def test_fused_td1_rejects_mismatched_network():
         ops.call("dpac_mlp_rows_fwd_td1", ctypes.byref(eq), _lib.F64, N * B, ctypes.byref(view.struct),
                  ctypes.c_void_p(rows.data_ptr()), 20, ctypes.c_void_p(u.data_ptr()),
                  ctypes.c_void_p(data.dw.data_ptr()), ctypes.c_void_p(rows.data_ptr()), None,
-                 ops._stream(rows))
+                 None, None, ops._stream(rows))
 
 
 @pytest.mark.parametrize("name,d", [("LQR", 4), ("LQR_var", 10)])

@@ -114,7 +114,7 @@ def test_rows_in_range_keep_the_split_fp16_path():
 
 def _rollout_and_bptt(net, eqp, x0, dw, T, N):
     """The actor's forward with saves, its BPTT chain G and the parameter gradients, as
-    ops.actor_bptt_grads forms them (dpac_rollout_nn_fwd_masked, dpac_rollout_nn_bwd_masked,
+    ops.actor_bptt_grads forms them (dpac_rollout_nn_fwd, dpac_rollout_nn_bwd,
     dpac_mlp_param_grads)."""
     view = net.mlp_view()
     x, dt, coef, u, y, disc, saves = ops.rollout_nn(eqp, _lib.SCHEME_ADAPTIVE, x0, dw, T, N, view,
@@ -140,8 +140,8 @@ def _rollout_and_bptt(net, eqp, x0, dw, T, N):
 
 @pytest.mark.parametrize("name,big_layer", [("LQR", 1), ("EKN", 2), ("LQR", 0)])
 def test_fused_rollout_and_bptt_out_of_range_fall_back_to_f32(name, big_layer, monkeypatch):
-    """dpac_rollout_nn_fwd_masked / dpac_rollout_nn_bwd_masked (the actor) with BN_l times 2^20 at
-    B = 2048 (16-row tiles): the fallback writes the same x, dt, coef, u, cost, saves, mask and
+    """dpac_rollout_nn_fwd / dpac_rollout_nn_bwd with the sign-bit mask (the actor), BN_l times 2^20
+    at B = 2048 (16-row tiles): the fallback writes the same x, dt, coef, u, cost, saves, mask and
     BPTT chain G as the f32 kernels, and the parameter gradients match theirs."""
     cfg = full_config(name, 20, N=16, hidden=(200, 200, 200), dtype="float32")
     eqp = getattr(peq, name)(cfg.eqn_config).params()

@@ -69,14 +69,14 @@ def main():
         def split_bwd():
             gG = ops.td_assemble_bwd(eqp, x, u, data.dw, dt, coef, g_y)
             ops.call("dpac_mlp_rows_bwd", _lib.F32, R, ops.ctypes.byref(bview.struct),
-                     ops._ptr_array(wt), ops._ptr_array(wt_km), ops._ptr(z), ops._ptr(gG),
+                     ops._ptr_array(wt), ops._ptr_array(wt_km), ops._ptr(z), None, ops._ptr(gG),
                      ops._ptr(Gbuf), None, ops._stream(rows))
 
         def fused_bwd():
             gg = ops.td_assemble_bwd_gdot(eqp, dt, coef, g_y)
             ops.call("dpac_mlp_rows_bwd_td1", ops.ctypes.byref(eqp), _lib.F32, R,
                      ops.ctypes.byref(bview.struct), ops._ptr_array(wt), ops._ptr_array(wt_km),
-                     ops._ptr(z), ops.ctypes.c_void_p(rows.data_ptr()), rows.stride(0),
+                     ops._ptr(z), None, ops.ctypes.c_void_p(rows.data_ptr()), rows.stride(0),
                      ops._ptr(u_rows), ops._ptr(dw_rows), ops._ptr(gg), ops._ptr(Gbuf), None,
                      ops._stream(rows))
 

@@ -56,11 +56,11 @@ def main():
 
         def bwd():
             _lib.call("dpac_mlp_rows_bwd", _lib.F32, R, ctypes.byref(bview.struct), ops._ptr_array(wt),
-                      ops._ptr_array(wt_km), ops._ptr(z), ops._ptr(g), ops._ptr(G), None, ops._stream(x))
+                      ops._ptr_array(wt_km), ops._ptr(z), None, ops._ptr(g), ops._ptr(G), None, ops._stream(x))
         _, _, mask = ops.mlp_rows(view, x, save=True, mask=True)
 
         def bwd_masked():
-            _lib.call("dpac_mlp_rows_bwd_masked", _lib.F32, R, ctypes.byref(bview.struct), ops._ptr_array(wt),
+            _lib.call("dpac_mlp_rows_bwd", _lib.F32, R, ctypes.byref(bview.struct), ops._ptr_array(wt),
                       ops._ptr_array(wt_km), ops._ptr(z), ops._ptr(mask), ops._ptr(g), ops._ptr(G), None,
                       ops._stream(x))
         res = {"fwd": timeit(lambda: ops.mlp_rows(view, x, save=False)),
