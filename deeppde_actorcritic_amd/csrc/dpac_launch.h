@@ -36,22 +36,11 @@ int width_sum(const NnMlp<T>& m) {
   return wsum;
 }
 
-// Row tile of the fused NN rollout for float: 4 (4x4x1 MFMA blocks) or 16
-// (16x16x4 tiles; float64 always uses these); by default 4 for B <= 1024.
-// DPAC_NN_TILE=4 / 16 forces one (tests compare the two).
 // BPTT kernel: 2 = k_rollout_nn_bwd2 (stager + writer wavefronts, default), 1 = k_rollout_nn_bwd.
+// DPAC_BPTT=1 / 2 forces one (tests compare the two).
 inline int bptt_kernel() {
   const char* e = getenv("DPAC_BPTT");  // read per launch: tests switch it in-process
   return (e && e[0] == '1') ? 1 : 2;
-}
-
-// Dynamic LDS of k_rollout_nn_bwd2: at least what it needs; DPAC_BPTT_LDS=max claims the
-// whole LDS so no other kernel's workgroup shares a BPTT CU (timing experiments).
-inline uint32_t bptt_lds(uint32_t need, uint32_t cap) {
-  const char* e = getenv("DPAC_BPTT_LDS");  // read per launch
-  if (!e) return need;
-  const uint32_t v = (e[0] == 'm') ? cap : (uint32_t)atoi(e);
-  return v > need ? (v < cap ? v : cap) : need;
 }
 
 // Analytic rollout with dw staged through LDS (k_rollout_staged, default) or read directly
@@ -61,6 +50,9 @@ inline bool rollout_staged() {
   return !(e && e[0] == '0');
 }
 
+// Row tile of the fused NN rollout for float: 4 (4x4x1 MFMA blocks) or 16
+// (16x16x4 tiles; float64 always uses these); by default 4 for B <= 1024.
+// DPAC_NN_TILE=4 / 16 forces one (tests compare the two).
 inline int nn_tile_rows() {
   const char* e = getenv("DPAC_NN_TILE");  // read per launch: tests switch it in-process
   const int v = e ? atoi(e) : 0;
@@ -296,7 +288,7 @@ int launch_rollout_nn_bwd(const OpArgs& a, const E& eq, const DevConsts<T>& c, h
         const Plan pl(width_sum(m), m.ztot, true, r.mb);
         NnBackArgs<T> f = r;
         f.guard = m.status;
-        err = launch_bwd2_mask<T, E, D>(eq, c, m, f, a.scheme, bptt_lds(pl.total, Plan::kMaxDyn), s);
+        err = launch_bwd2_mask<T, E, D>(eq, c, m, f, a.scheme, pl.total, s);
       }
       return (int)err;
     }
@@ -304,7 +296,7 @@ int launch_rollout_nn_bwd(const OpArgs& a, const E& eq, const DevConsts<T>& c, h
   if (gphase == DPAC_GUARD_FALLBACK_ONLY) return 0;  // phase 1 did the whole work
   if (bptt_kernel() == 2) {
     const Plan pl(width_sum(m), m.ztot, true, r.mask ? r.mb : 0);
-    const uint32_t lds = bptt_lds(pl.total, Plan::kMaxDyn);
+    const uint32_t lds = pl.total;
     if constexpr (kNnFastOk<T>) {
       if (r.mask) return (int)launch_bwd2_mask<T, E, D>(eq, c, m, r, a.scheme, lds, s);
     }

@@ -318,7 +318,7 @@ struct X3Args {
   float* gdot;
   const float* g_gdot;
   uint32_t* status;  // the range guard (dpac_mlp.status), or null
-  // the hidden activations' sign bits (dpac.h dpac_mlp_rows_fwd_masked): per hidden layer h
+  // the hidden activations' sign bits (dpac.h dpac_mlp_rows_fwd, save_mask): per hidden layer h
   // (1..L) and 64-row block b, 512 words; word ((h - 1) nblk + b) 512 + 64 w + 16 q + r holds at
   // bit 4 (2 rt + j) + e whether BN_h's output of row 64 b + 16 rt + r, feature 16 (w + 8 j) +
   // 4 q + e, is > 0 — exactly the nibbles lane 16 q + r of wave w holds in the 64-row forward

@@ -19,31 +19,12 @@
 #pragma once
 // Included by dpac_kernels.h inside namespace dpac.
 
-#ifndef DPAC_NN_WAVES
-#define DPAC_NN_WAVES 8  // 2 wavefronts per SIMD: measured 18.2 -> 15.4 us per step at lqr_d20
-#endif
 constexpr int kNnRows = 16;  // trajectories per workgroup = one MFMA row tile
-constexpr int kNnWaves = DPAC_NN_WAVES;
+constexpr int kNnWaves = 8;  // 2 wavefronts per SIMD: measured 18.2 -> 15.4 us per step at lqr_d20
 constexpr int kNnThreads = 64 * kNnWaves;
-#ifndef DPAC_NN_LD_PAD
-#define DPAC_NN_LD_PAD 4  // LDS row stride = max width + pad (elements)
-#endif
-constexpr int kNnLd = DPAC_MLP_MAX_WIDTH + DPAC_NN_LD_PAD;  // LDS row stride (elements)
+constexpr int kNnLd = DPAC_MLP_MAX_WIDTH + 4;  // LDS row stride = max width + pad (elements)
 constexpr int kNnMaxTilesPerWave = (DPAC_MLP_MAX_WIDTH / 16 + kNnWaves - 1) / kNnWaves;
-#ifndef DPAC_NN_PREFETCH
-#define DPAC_NN_PREFETCH 4  // measured 14.9 -> 14.7 us per step (12, 16: slower)
-#endif
-constexpr int kNnPrefetch = DPAC_NN_PREFETCH;
-#ifndef DPAC_NN_KM_PG
-#define DPAC_NN_KM_PG 2  // k-major path: groups of 4 k-steps of B in flight per tile
-#endif  // k-steps of B in flight per tile
-#ifndef DPAC_NN_ABLATE
-#define DPAC_NN_ABLATE 0  // timing-only builds: 1 = constant weights, 2 = skip the MLP
-#endif
-#ifndef DPAC_BWD_ABLATE
-#define DPAC_BWD_ABLATE 0  // timing-only BPTT builds (bits): 1 = no z loads, 2 = no G stores,
-                           // 4 = no step-lane loads, 8 = skip the MLP chain
-#endif
+constexpr int kNnPrefetch = 4;  // measured 14.9 -> 14.7 us per step (12, 16: slower)
 // Timing-only builds (-DDPAC_NN_TRACE=1): lane 0 of every wavefront of workgroup 0
 // records the shader clock at fixed points of the first 64 steps into a per-TU device
 // table, read back by dpac_debug_trace (tools/probe_trace.py).
@@ -141,7 +122,7 @@ __device__ __forceinline__ void mfma_rows16_km(const float* in, int K, int Nout,
     return v;
   };
   auto loadA = [&](int s) { return *reinterpret_cast<const f4*>(arow + 16 * (s < ng ? s : ng - 1)); };
-  constexpr int PG = DPAC_NN_KM_PG;  // groups (4 k-steps each) of B in flight per tile
+  constexpr int PG = 2;  // groups (4 k-steps each) of B in flight per tile
   f4 bq[PG][NT], av[PG];
 #pragma unroll
   for (int q = 0; q < PG; ++q) {
@@ -173,18 +154,7 @@ __device__ __forceinline__ void mfma_rows16_km(const float* in, int K, int Nout,
   }
 }
 
-#ifndef DPAC_NN_KMS
-#define DPAC_NN_KMS 1  // 1: static-K (fully unrolled) k-major layers for the specialised K16
-#endif
-#ifndef DPAC_NN_SAVE_NT
-#define DPAC_NN_SAVE_NT 0
-#endif
-#ifndef DPAC_NN_PIN
-#define DPAC_NN_PIN 1  // sched_barrier after each k group of the static-K layers
-#endif
-#ifndef DPAC_NN_KMS_PG
-#define DPAC_NN_KMS_PG 2  // groups of B in flight per tile in the static-K layer (3, 4 measured slower)
-#endif
+constexpr int kNnKmsPg = 2;  // groups of B in flight per tile in the static-K layer (3, 4 measured slower)
 
 // mfma_rows16_km with the group count NG = K16 / 16 a template constant: the K loop is
 // straight-line code, so the A operand of every group is read from LDS up front (NG
@@ -196,16 +166,13 @@ __device__ __forceinline__ void mfma_rows16_kms(const float* in, int Nout, const
   using MF = Mfma<float>;
   typedef float f4 __attribute__((ext_vector_type(4)));
   constexpr int K16 = 16 * NG;
-  constexpr int PG = DPAC_NN_KMS_PG < NG ? DPAC_NN_KMS_PG : NG;
+  constexpr int PG = kNnKmsPg < NG ? kNnKmsPg : NG;
   const int col_l = lane & 15, kq = lane >> 4;
   const __amdgpu_buffer_rsrc_t rW = make_rsrc(Wkm, (uint32_t)(Nout * K16 * 4));
   uint32_t voff[NT];
   MF::acc_t acc[NT];
   typename EPI::Col cc[NT];
   auto loadB = [&](int s, int j) {
-#if DPAC_NN_ABLATE == 1
-    return f4{1e-3f * (j + 1), 1e-3f * s, 0.5f, -0.25f};  // timing only: no weight traffic
-#endif
     uint32_t w[4];
     buf_load_dwords<4>(rW, voff[j] + (uint32_t)(s * 64), w);
     f4 v;
@@ -243,9 +210,7 @@ __device__ __forceinline__ void mfma_rows16_kms(const float* in, int Nout, const
       for (int e = 0; e < 4; ++e) acc[j] = MF::mma(as[e], b[s % PG][j][e], acc[j]);
       if (s + PG < NG) b[s % PG][j] = loadB(s + PG, j);
     }
-#if DPAC_NN_PIN
     __builtin_amdgcn_sched_barrier(0);  // keep the B ring's loads PG groups ahead (see kms_pre)
-#endif
   }
 #pragma unroll
   for (int j = 0; j < NT; ++j) {
@@ -260,12 +225,10 @@ __device__ __forceinline__ void mfma_rows16(const T* in, int K, int Nout, const 
                                             int wave, int lane, EPI& epi) {
   if constexpr (sizeof(T) == 4) {
     if (Wkm) {  // block-uniform
-#if DPAC_NN_KMS
       // the actor shapes' K16 (d = 20 -> 32; hidden 200 -> 208) as straight-line layers
       const int ng = (K + 15) / 16;
       if (ng == 2) { mfma_rows16_kms<NT, 2>(in, Nout, Wkm, wave, lane, epi); return; }
       if (ng == 13) { mfma_rows16_kms<NT, 13>(in, Nout, Wkm, wave, lane, epi); return; }
-#endif
       mfma_rows16_km<NT>(in, K, Nout, Wkm, wave, lane, epi);
       return;
     }
@@ -292,9 +255,6 @@ __device__ __forceinline__ void mfma_rows16(const T* in, int K, int Nout, const 
   // read 0, so the ring needs no predicate.  A is read one ring iteration ahead;
   // k-steps past the last are clamped to it (their B is 0, the product adds nothing).
   auto loadB = [&](int ks, int j) {
-#if DPAC_NN_ABLATE == 1
-    return T(1e-3) * T(j + 1) + T(ks & 1);  // timing only: no weight traffic
-#endif
     uint32_t w[sizeof(T) / 4];
     buf_load_dwords<sizeof(T) / 4>(rW, voff[j] + (uint32_t)ks * kstep_bytes, w);
     T v;
@@ -331,10 +291,6 @@ __device__ __forceinline__ void mfma_rows16(const T* in, int K, int Nout, const 
     for (int i = 0; i < 4; ++i) epi.store(i, MF::row(lane, i), col, col < Nout, acc[j][i], cc[j]);
   }
 }
-
-#ifndef DPAC_NN_SPLITK
-#define DPAC_NN_SPLITK 1  // narrow layers (Nout <= 32) split K over all wavefronts
-#endif
 
 // A narrow layer (Nout <= 32, i.e. NT <= 2 column tiles) as a split-K product: a
 // column split would leave all but NT wavefronts idle through a K/4-long
@@ -425,23 +381,19 @@ __device__ __forceinline__ void mfma_rows16_splitk(const T* in, int K, int Nout,
 
 // Whether mfma_layer runs the layer as the split-K product (two internal barriers).
 __device__ __forceinline__ bool nn_splitk_layer(int K, int Nout) {
-  return DPAC_NN_SPLITK && kNnWaves == 8 && Nout <= 32 && K > 32;
+  return Nout <= 32 && K > 32;
 }
 
 // Run mfma_rows16 with this wave's (wave-uniform) tile count.
 template <typename T, class EPI>
 __device__ __forceinline__ void mfma_layer(const T* in, int K, int Nout, const T* W, const T* Wkm,
                                            int wave, int lane, EPI& epi) {
-#if DPAC_NN_SPLITK
-  if constexpr (kNnWaves == 8) {
-    static_assert(8 * 16 * 32 <= kNnRows * kNnLd, "partials fit the output image");
-    if (Nout <= 32 && K > 32) {  // block-uniform
-      if (Nout <= 16) mfma_rows16_splitk<T, 1>(in, K, Nout, W, Wkm, wave, lane, epi, epi.out);
-      else mfma_rows16_splitk<T, 2>(in, K, Nout, W, Wkm, wave, lane, epi, epi.out);
-      return;
-    }
+  static_assert(8 * 16 * 32 <= kNnRows * kNnLd, "partials fit the output image");
+  if (nn_splitk_layer(K, Nout)) {  // block-uniform: narrow layers split K over all wavefronts
+    if (Nout <= 16) mfma_rows16_splitk<T, 1>(in, K, Nout, W, Wkm, wave, lane, epi, epi.out);
+    else mfma_rows16_splitk<T, 2>(in, K, Nout, W, Wkm, wave, lane, epi, epi.out);
+    return;
   }
-#endif
   const int ntiles = (Nout + 15) / 16;
   const int mine = ntiles > wave ? (ntiles - wave + kNnWaves - 1) / kNnWaves : 0;
   static_assert(kNnMaxTilesPerWave <= 4, "dispatch below covers 1..4 tiles");
@@ -476,8 +428,8 @@ struct NarrowIn {   // B of a K16 <= 32 layer: [group s][tile j], tiles j >= min
 struct NarrowOut {  // B of the split-K layer: [group g of the wave's K slice][tile j]
   nnf4 b[2][2];
 };
-struct WidePre {    // the first DPAC_NN_KMS_PG groups of a wide layer's B
-  nnf4 b[DPAC_NN_KMS_PG][2];
+struct WidePre {    // the first kNnKmsPg groups of a wide layer's B
+  nnf4 b[kNnKmsPg][2];
 };
 
 __device__ __forceinline__ nnf4 nn_load_f4(__amdgpu_buffer_rsrc_t r, uint32_t off) {
@@ -533,7 +485,7 @@ __device__ __forceinline__ void load_wide_pre(WidePre& r, const float* Wkm, int 
   for (int j = 0; j < 2; ++j) {
     const int col = (wave + kNnWaves * j) * 16 + col_l;
 #pragma unroll
-    for (int q = 0; q < DPAC_NN_KMS_PG; ++q)
+    for (int q = 0; q < kNnKmsPg; ++q)
       r.b[q][j] = nn_load_f4(rW, col < Nout ? (uint32_t)((col * K16 + 4 * kq + 16 * q) * 4) : kOOB);
   }
 }
@@ -582,9 +534,6 @@ __device__ __forceinline__ void mfma_rows16_res(const float* in, int Nout, const
   }
 }
 
-#ifndef DPAC_NN_PRE_EARLY
-#define DPAC_NN_PRE_EARLY 1  // 0: the next layer's prefetch after the epilogue (timing knob)
-#endif
 struct NoNext {
   __device__ __forceinline__ void operator()() const {}
 };
@@ -597,8 +546,8 @@ __device__ __forceinline__ void mfma_rows16_kms_pre(const float* in, int Nout, c
                                                     int wave, int lane, EPI& epi, NX nx = NX{}) {
   using MF = Mfma<float>;
   constexpr int K16 = 16 * NG;
-  constexpr int PG = DPAC_NN_KMS_PG < NG ? DPAC_NN_KMS_PG : NG;
-  static_assert(PG == DPAC_NN_KMS_PG, "the prefetch holds PG groups");
+  constexpr int PG = kNnKmsPg < NG ? kNnKmsPg : NG;
+  static_assert(PG == kNnKmsPg, "the prefetch holds PG groups");
   const int col_l = lane & 15, kq = lane >> 4;
   const __amdgpu_buffer_rsrc_t rW = make_rsrc(Wkm, (uint32_t)(Nout * K16 * 4));
   uint32_t voff[NT];
@@ -635,18 +584,13 @@ __device__ __forceinline__ void mfma_rows16_kms_pre(const float* in, int Nout, c
     // (one load in flight, the L2 latency exposed every 4 MFMAs)
     __builtin_amdgcn_sched_barrier(0);
   }
-#if DPAC_NN_PRE_EARLY
   nx();
-#endif
 #pragma unroll
   for (int j = 0; j < NT; ++j) {
     const int col = (wave + kNnWaves * j) * 16 + col_l;
 #pragma unroll
     for (int i = 0; i < 4; ++i) epi.store(i, MF::row(lane, i), col, col < Nout, acc[j][i], cc[j]);
   }
-#if !DPAC_NN_PRE_EARLY
-  nx();
-#endif
 }
 
 // mfma_rows16_splitk's k-major branch with the wave's slice of B in registers
@@ -693,8 +637,7 @@ __device__ __forceinline__ void mfma_rows16_splitk_res(const float* in, int K, i
 // DPAC_NN_FAST=0 forces the generic path (tests compare the two bit for bit).
 template <typename T>
 inline bool nn_fast_host(int L, const int* width, const void* const* km, int kin, int kout) {
-  if (!std::is_same<T, float>::value || L < 1 || kin > 32 || kout > 32 || kNnWaves != 8 || !DPAC_NN_SPLITK)
-    return false;
+  if (!std::is_same<T, float>::value || L < 1 || kin > 32 || kout > 32) return false;
   const char* e = getenv("DPAC_NN_FAST");  // read per launch
   if (e && e[0] == '0') return false;
   for (int i = 1; i <= L; ++i)
@@ -757,11 +700,7 @@ struct FwdEpi {
     store(0, row, col, valid, z, k);
   }
   __device__ __forceinline__ void store(int, int row, int col, bool valid, T z, const Col& k) const {
-#if DPAC_NN_SAVE_NT  // timing knob: non-temporal z saves
-    if (save && valid && row < rows_live) __builtin_nontemporal_store(z, save + row * save_stride + col);
-#else
     if (save && valid && row < rows_live) save[row * save_stride + col] = z;
-#endif
     T yv = bias ? z + k.bb : z;          // addmm(b, y, W) (solver.py:270)
     yv = k.sh + yv * k.s;                // addcmul(beta, y, gamma/sqrt(1+eps))
     if (hidden) yv = yv + fmax(yv, T(0));  // y + relu(y) (solver.py:269)
@@ -817,11 +756,7 @@ struct BwdEpi {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int row = Mfma<T>::row(lane, i);
-#if DPAC_BWD_ABLATE & 1
-        k.z[i] = T(row - col);
-#else
         k.z[i] = (valid && row < rows_live) ? z[row * z_stride + col] : T(0);
-#endif
       }
     }
     return k;
@@ -844,9 +779,7 @@ struct BwdEpi {
       const T yv = k.sh + k.z * k.s;
       v = acc * (yv > T(0) ? T(2) : T(1));
     }
-#if !(DPAC_BWD_ABLATE & 2)
     if (valid && row < rows_live) g[row * g_stride + col] = v;
-#endif
     out[row * kNnLd + col] = valid ? v : T(0);
   }
   __device__ __forceinline__ void store(int i, int row, int col, bool valid, T acc, const Col& k) const {
@@ -855,9 +788,7 @@ struct BwdEpi {
       const T yv = k.sh + k.z[i] * k.s;  // the forward's BN_l output, same expression
       v = acc * (yv > T(0) ? T(2) : T(1));  // d(y + relu(y))/dy
     }
-#if !(DPAC_BWD_ABLATE & 2)
     if (valid && row < rows_live) g[row * g_stride + col] = v;
-#endif
     out[row * kNnLd + col] = valid ? v : T(0);
   }
 };
@@ -925,20 +856,11 @@ __global__ __launch_bounds__(kNnThreads) void k_rollout_nn_bwd(const E eq, const
     const int64_t rowt = (int64_t)t * a.B;
     if (stepper) {
       T x[M], u[MC], dwv[M], gu[MC], gdn;
-#if DPAC_BWD_ABLATE & 4
-#pragma unroll
-      for (int m = 0; m < M; ++m) x[m] = dwv[m] = T(0.01) * T(m + t);
-#pragma unroll
-      for (int m = 0; m < MC; ++m) u[m] = T(0.02) * T(m - t);
-      const Flags fl = Flags::decode(2 - (t & 1));
-      const T dsc = T(1);
-#else
       own.load_masked(a.x + (rowt + lc.b) * D, x);
       own.load_masked(a.dw + (rowt + lc.b) * D, dwv);
       ownu.load_masked(a.u + (rowt + lc.b) * CD, u);
       const Flags fl = Flags::decode(a.flag[rowt + lc.b]);
       const T dsc = a.disc_t[rowt + lc.b];
-#endif
       step_vjp<T, E, SCHEME>(eq, c, x, u, dwv, fl, dsc, lam, gD, gy, gxd, gu, gdn);
       gD = gdn;
       // gradient at the network output, through the Eikonal head (solver.py:272-274)
@@ -979,7 +901,7 @@ __global__ __launch_bounds__(kNnThreads) void k_rollout_nn_bwd(const E eq, const
     // ---- input-gradient chain through the MLP (all four wavefronts) ----
     const T* in = s_pq[0];
     int pq = 1;
-    for (int l = L; l >= ((DPAC_BWD_ABLATE & 8) ? L + 1 : 0); --l) {
+    for (int l = L; l >= 0; --l) {
       T* out = s_pq[pq];
       BwdEpi<T> epi{l >= 1 ? mlp.scale[l] : nullptr, l >= 1 ? mlp.shift[l] : nullptr,
                     a.z + (rowt + row0) * mlp.ztot + mlp.zoff[l], mlp.ztot, rows_live, lane, out,
@@ -1075,7 +997,7 @@ __global__ __launch_bounds__(kNnThreads) void k_rollout_nn(const E eq, const Dev
     // ---- actor MLP on MFMA (all four wavefronts) ----
     const T* in = s_x0;
     int pq = 0;
-    for (int l = 0; l <= (DPAC_NN_ABLATE == 2 ? -1 : L); ++l) {  // ablation 2: no MLP (timing)
+    for (int l = 0; l <= L; ++l) {
       T* out = s_pq[pq];
       FwdEpi<T> epi{mlp.scale[l + 1], mlp.shift[l + 1], l == L ? mlp.bias : nullptr, l < L, out,
                     a.save_z ? a.save_z + ((int64_t)t * a.B + row0) * mlp.ztot + mlp.zoff[l + 1] : nullptr,

@@ -21,24 +21,6 @@
 // Included by dpac_kernels.h inside namespace dpac, after dpac_rollout_nn.h.
 
 constexpr int kNnBwdThreads = kNnThreads + 128;  // + stager + writer
-#ifndef DPAC_BWD2_GNT
-#define DPAC_BWD2_GNT 0  // timing knob: non-temporal G stores from the writer wave
-#endif
-#ifndef DPAC_BWD2_DMA_NT
-#define DPAC_BWD2_DMA_NT 0  // timing knob: the stager's LDS-DMA with the nt cache policy
-#endif
-#if DPAC_BWD2_DMA_NT
-#define DPAC_BWD2_DMA_POL " nt"
-#else
-#define DPAC_BWD2_DMA_POL ""
-#endif
-#ifndef DPAC_BWD2_ZREG
-#define DPAC_BWD2_ZREG 0  // timing knob: stage z through the stager's VGPRs instead of LDS-DMA
-#endif
-#ifndef DPAC_BWD2_ABLATE
-#define DPAC_BWD2_ABLATE 0  // timing-only builds (bits): 1 = the stager copies nothing, 2 = the writer
-                           // does nothing, 4 = the writer reads LDS but stores nothing
-#endif
 
 __device__ __forceinline__ void nn_bar() {
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -67,7 +49,7 @@ __device__ __forceinline__ void wave_copy_lds(const void* src, uint32_t bytes, u
     const uint32_t m0 = __builtin_amdgcn_readfirstlane(lds0 + k * 64 * SZ);
     int keep;
     if constexpr (SZ == 16)
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" DPAC_BWD2_DMA_POL "\n\ts_mov_b32 m0, %0"
+      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                    : "=&s"(keep) : "v"(gp), "s"(m0) : "memory");
     else
       asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
@@ -210,21 +192,10 @@ __device__ __forceinline__ void write_G_rows(const T* img, int per_row, T* G, in
     v1 = *reinterpret_cast<const vec*>(img + (rb1 < rows_live ? rb1 : 0) * kNnLd + q * V);
     v2 = *reinterpret_cast<const vec*>(img + (rc < rows_live ? rc : 0) * kNnLd + q * V);
     v3 = *reinterpret_cast<const vec*>(img + (rd < rows_live ? rd : 0) * kNnLd + q * V);
-#if DPAC_BWD2_ABLATE & 4
-    asm volatile("" ::"v"(v0), "v"(v1), "v"(v2), "v"(v3));
-    continue;
-#endif
-#if DPAC_BWD2_GNT  // timing knob: non-temporal G stores
-    if (act && ra < rows_live) __builtin_nontemporal_store(v0, reinterpret_cast<vec*>(G + ra * gtot + goff + q * V));
-    if (act && rb1 < rows_live) __builtin_nontemporal_store(v1, reinterpret_cast<vec*>(G + rb1 * gtot + goff + q * V));
-    if (act && rc < rows_live) __builtin_nontemporal_store(v2, reinterpret_cast<vec*>(G + rc * gtot + goff + q * V));
-    if (act && rd < rows_live) __builtin_nontemporal_store(v3, reinterpret_cast<vec*>(G + rd * gtot + goff + q * V));
-#else
     if (act && ra < rows_live) *reinterpret_cast<vec*>(G + ra * gtot + goff + q * V) = v0;
     if (act && rb1 < rows_live) *reinterpret_cast<vec*>(G + rb1 * gtot + goff + q * V) = v1;
     if (act && rc < rows_live) *reinterpret_cast<vec*>(G + rc * gtot + goff + q * V) = v2;
     if (act && rd < rows_live) *reinterpret_cast<vec*>(G + rd * gtot + goff + q * V) = v3;
-#endif
   }
 }
 
@@ -252,8 +223,8 @@ __global__ __launch_bounds__(kNnBwdThreads) void k_rollout_nn_bwd2(const E eq, c
   if (a.guard && !x3_status_set(a.guard)) return;  // a fallback launch: only once the x3 kernel fell back
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid / 64), lane = tid % 64;
-  const bool stager = wave == kNnWaves && !(DPAC_BWD2_ABLATE & 1);
-  const bool writer = wave == kNnWaves + 1 && !(DPAC_BWD2_ABLATE & 2);
+  const bool stager = wave == kNnWaves;
+  const bool writer = wave == kNnWaves + 1;
   const int64_t row0 = (int64_t)blockIdx.x * kNnRows;
   const int rows_live = (int)((a.B - row0) < kNnRows ? (a.B - row0) : kNnRows);
   const bool stepper = tid < kNnRows * P;
@@ -291,30 +262,8 @@ __global__ __launch_bounds__(kNnBwdThreads) void k_rollout_nn_bwd2(const E eq, c
     }
     if constexpr (ZST) {
       const int64_t rt = (int64_t)ts * a.B + row0;
-#if DPAC_BWD2_ZREG
-      // timing knob: the z share through the stager's VGPRs (dwordx4 loads, ds_write_b128)
-      // instead of LDS-DMA
-      const uint32_t bytes = (uint32_t)(rows_live * mlp.ztot * sizeof(T));
-      const uint32_t pieces = (bytes + 1023) / 1024;
-      const uint32_t k0 = pieces * part / kZParts, k1 = pieces * (part + 1) / kZParts;
-      const __amdgpu_buffer_rsrc_t rz = make_rsrc(a.z + rt * mlp.ztot, bytes);
-      unsigned char* dst = s_dyn + pl.z + (uint32_t)par * pl.zpar;
-      typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-      u4 v[16];
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const uint32_t off = ((k0 + q) * 64 + (uint32_t)lane) * 16;
-        uint32_t w[4];
-        buf_load_dwords<4>(rz, (k0 + q < k1) ? off : kOOB, w);
-        v[q] = u4{w[0], w[1], w[2], w[3]};
-      }
-#pragma unroll
-      for (int q = 0; q < 16; ++q)
-        if (k0 + q < k1) *reinterpret_cast<u4*>(dst + ((k0 + q) * 64 + (uint32_t)lane) * 16) = v[q];
-#else
       wave_copy_lds<16>(a.z + rt * mlp.ztot, (uint32_t)(rows_live * mlp.ztot * sizeof(T)),
                         s_dyn + pl.z + (uint32_t)par * pl.zpar, lane, part, kZParts);
-#endif
     }
   };
 

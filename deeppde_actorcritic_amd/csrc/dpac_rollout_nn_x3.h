@@ -44,10 +44,8 @@ typedef _Float16 nxh8 __attribute__((ext_vector_type(8)));
 typedef _Float16 nxh4 __attribute__((ext_vector_type(4)));
 typedef float nxf4 __attribute__((ext_vector_type(4)));
 
-#ifndef DPAC_NX_LDPAD
-#define DPAC_NX_LDPAD 16  // halves of padding per image row (a multiple of 8: 16-byte rows)
-#endif
-constexpr int kNxLd = 64 * 8 + DPAC_NX_LDPAD;  // halves per row of a hidden image (K <= 256): 264 dwords = 8 mod 64
+// halves per row of a hidden image (K <= 256) + 16 of padding (a multiple of 8: 16-byte rows): 264 dwords = 8 mod 64
+constexpr int kNxLd = 64 * 8 + 16;
 constexpr int kNxLd0 = 64 + 8;       // halves per row of the narrow input image (K <= 32): 36 dwords
 constexpr int kNxPartLd = 36;        // floats per row of a split-K partial (conflict-free b128 writes)
 constexpr int kNxWide = 7;           // 32-k chunks of a 193..224-wide K
@@ -55,10 +53,6 @@ constexpr int kNxWide = 7;           // 32-k chunks of a 193..224-wide K
 #define DPAC_NX_RING 4               // wide layers: chunks of weights in flight (VGPR budget: 16 per chunk)
 #endif
 constexpr int kNxRing = DPAC_NX_RING;
-#ifndef DPAC_NX_ABLATE
-#define DPAC_NX_ABLATE 0  // timing-only builds (bits): 1 = no weight loads (constant weights), 2 = no z / G /
-                          // mask stores, 4 = no LDS B-operand reads (constant activations)
-#endif
 constexpr int kNxBnHalf = DPAC_MLP_MAX_WIDTH;      // shift offset inside a layer's LDS BN image
 constexpr int kNxBnLd = 2 * DPAC_MLP_MAX_WIDTH;    // floats per hidden layer: scale | shift
 constexpr float kNxLo = 4096.f;      // 2^12
@@ -82,10 +76,6 @@ __device__ __forceinline__ nxf4 nx_mma(nxh8 a, nxh8 b, nxf4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 }
 
-#ifndef DPAC_NX_FOLD
-#define DPAC_NX_FOLD 1  // the narrow product after the last wide layer folded into its epilogue (round 5)
-#endif
-
 // four values split into hi / lo halves; true if one of them is outside the split range
 // (dpac.h dpac_mlp.status)
 __device__ __forceinline__ bool nx_split4(nxf4 v, nxh4& h, nxh4& l) {
@@ -97,47 +87,24 @@ __device__ __forceinline__ bool nx_split4(nxf4 v, nxh4& h, nxh4& l) {
   return x3_bad4(v[0], v[1], v[2], v[3]);
 }
 
-// Bank-conflict-free hidden images (round 6).  A row holds, per 32-k chunk,
-// 32 hi halves then 32 lo halves: eight 16-byte blocks.  The B-operand reads (lane l: row l & 15,
-// k block l >> 4, ds_read_b128) were conflict-free at the 264-dword row stride, but the
-// epilogue's two 8-byte writes per tile (ds_write_b64: 16 contiguous lanes = the 16 rows at one
-// k quad, banks (a/4) mod 32, row stride 8 mod 32) hit 4 distinct bank pairs: 4-way conflicts,
-// the bulk of the kernels' measured lds_conflict_frac (0.32 / 0.36).  Now:
-//  * the 16-byte blocks of rows 4..7 and 12..15 swap in pairs (block index XOR ((row >> 2) & 1));
-//  * a v_permlane16_swap per dword gives the lanes of even 16-lane rows (k quads 0, 2) the hi
-//    halves of their quad AND the next quad, and the odd rows the lo halves of both, so each
-//    lane stores ONE 16-byte block (ds_write_b128, 8 contiguous lanes per bank cycle).
-// Both the reads and the writes are then conflict-free under gfx950's LDS lane grouping
-// (MI355X_MICROARCH.md §LDS; checked exhaustively for every tile and chunk offline).
-#ifndef DPAC_NX_SWZ
-#define DPAC_NX_SWZ 0  // 0: unswizzled images, two 8-byte writes per tile (4-way write conflicts);
-                       // 1: swizzled, two 8-byte writes (2-way); 2: swizzled + permlane16 swap, one
-                       // 16-byte write (conflict-free)
-#endif
-__device__ __forceinline__ int nx_swz(int row) { return DPAC_NX_SWZ ? (row >> 2) & 1 : 0; }
+// Hidden images.  A row holds, per 32-k chunk, 32 hi halves then 32 lo halves: eight 16-byte
+// blocks, unswizzled.  The B-operand reads (lane l: row l & 15, k block l >> 4, ds_read_b128) are
+// conflict-free at the 264-dword row stride; the epilogue's two 8-byte writes per tile
+// (ds_write_b64: 16 contiguous lanes = the 16 rows at one k quad) hit 4 distinct bank pairs, a
+// 4-way conflict.  A row swizzle of the blocks with a permlane16 swap (one conflict-free 16-byte
+// write per tile) was tried and rejected: profiles/r06_call4_lds_swizzle_rejected.txt.
 
-// four consecutive features f0..f0+3 (f0 % 4 == 0) of one row, split; the wave's lanes exchange
-// halves (above) and each stores one 16-byte block.  ld = kNxLd (the swizzled hidden images).
-// True if one of the values is outside the split range (dpac.h dpac_mlp.status).
-__device__ __forceinline__ bool nx_put4(_Float16* img, int ld, int row, int f0, nxf4 v, int lane) {
-  typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+// four consecutive features f0..f0+3 (f0 % 4 == 0) of one row, split and stored as two 8-byte
+// writes: hi at block (f0 % 32) / 8, lo 4 blocks on (a 4-feature quad is half a block).  ld = kNxLd
+// (the hidden images).  True if one of the values is outside the split range (dpac.h
+// dpac_mlp.status).
+__device__ __forceinline__ bool nx_put4(_Float16* img, int ld, int row, int f0, nxf4 v) {
   nxh4 h, l;
   const bool bad = nx_split4(v, h, l);
-  if constexpr (DPAC_NX_SWZ < 2) {  // two 8-byte writes: hi at block (f0 % 32) / 8, lo 4 blocks on
-    const int blk = ((f0 & 31) >> 3) ^ nx_swz(row);  // (a 4-feature quad is half a block)
-    _Float16* p = img + row * ld + (f0 >> 5) * 64 + 8 * blk + (f0 & 4);
-    *reinterpret_cast<nxh4*>(p) = h;
-    *reinterpret_cast<nxh4*>(p + 32) = l;
-    return bad;
-  }
-  u32x2 hw = __builtin_bit_cast(u32x2, h), lw = __builtin_bit_cast(u32x2, l);
-  // odd 16-lane rows of hw <-> even rows of lw: even rows keep [h(q) | h(q + 1)], odd rows
-  // [l(q - 1) | l(q)]
-  const auto s0 = __builtin_amdgcn_permlane16_swap(hw[0], lw[0], false, false);
-  const auto s1 = __builtin_amdgcn_permlane16_swap(hw[1], lw[1], false, false);
-  const int q = lane >> 4;
-  _Float16* p = img + row * ld + (f0 >> 5) * 64 + 32 * (q & 1) + 16 * ((f0 >> 4) & 1) + 8 * ((q >> 1) ^ nx_swz(row));
-  *reinterpret_cast<uint4*>(p) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
+  const int blk = (f0 & 31) >> 3;
+  _Float16* p = img + row * ld + (f0 >> 5) * 64 + 8 * blk + (f0 & 4);
+  *reinterpret_cast<nxh4*>(p) = h;
+  *reinterpret_cast<nxh4*>(p + 32) = l;
   return bad;
 }
 
@@ -217,12 +184,6 @@ __device__ __forceinline__ void nx_loadw(nxh8 (&wh)[NC][2], nxh8 (&wl)[NC][2], c
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       const uint32_t o = (ok && c0 + c < nch) ? base + (uint32_t)((c0 + c) * 2048) : kOOB;
-#if DPAC_NX_ABLATE & 1
-      wh[c][j] = nxh8{(_Float16)(0.01f * c), (_Float16)0.02f, 0, 0, 0, 0, (_Float16)(0.001f * j), 0};
-      wl[c][j] = wh[c][j];
-      (void)o;
-      continue;
-#endif
       wh[c][j] = __builtin_bit_cast(nxh8, __builtin_amdgcn_raw_buffer_load_b128(r, (int)o, 0, 0));
       wl[c][j] = __builtin_bit_cast(nxh8, __builtin_amdgcn_raw_buffer_load_b128(r, (int)(o + 1024u), 0, 0));
     }
@@ -241,8 +202,7 @@ __device__ __forceinline__ void nx_prod(const _Float16* in, int c0, nxh8 (&wh)[N
                                         nxf4 (&acc)[2][3], int lane, const _Float16* W = nullptr, int Nout = 0,
                                         int nch = 0, int tA = 0, int tB = 0) {
   static_assert(RING ? NS == RING : NS == NC, "resident: one slot per chunk");
-  // the hidden images' 16-byte blocks are swizzled by row (nx_swz); the narrow input image is not
-  const int kq = LD == kNxLd ? ((lane >> 4) ^ nx_swz(lane & 15)) : (lane >> 4);
+  const int kq = lane >> 4;
   const _Float16* b = in + (lane & 15) * LD + c0 * 64 + 8 * kq;
 #pragma unroll
   for (int j = 0; j < 2; ++j)
@@ -258,18 +218,13 @@ __device__ __forceinline__ void nx_prod(const _Float16* in, int c0, nxh8 (&wh)[N
       base[j] = tile < ntiles ? (uint32_t)(tile * nch * 2048 + 16 * lane) : kOOB;
     }
   }
-#if DPAC_NX_ABLATE & 4
-  nxh8 bh = nxh8{(_Float16)0.5f, 0, 0, (_Float16)(0.25f * c0), 0, 0, 0, 0}, bl = bh;
-  (void)b;
-#else
   nxh8 bh = *reinterpret_cast<const nxh8*>(b), bl = *reinterpret_cast<const nxh8*>(b + 32);
-#endif
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
     constexpr int kS = RING > 0 ? RING : NC;
     const int sl = c % kS;
     nxh8 nh = bh, nl = bl;
-    if (c + 1 < NC && !(DPAC_NX_ABLATE & 4)) {
+    if (c + 1 < NC) {
       nh = *reinterpret_cast<const nxh8*>(b + (c + 1) * 64);
       nl = *reinterpret_cast<const nxh8*>(b + (c + 1) * 64 + 32);
     }
@@ -280,7 +235,7 @@ __device__ __forceinline__ void nx_prod(const _Float16* in, int c0, nxh8 (&wh)[N
       acc[j][2] = nx_mma(wl[sl][j], bh, acc[j][2]);
     }
     if constexpr (RING > 0) {
-      if (c + RING < NC && !(DPAC_NX_ABLATE & 1)) {  // refill the slot just used
+      if (c + RING < NC) {  // refill the slot just used
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
           const uint32_t o = base[j] + (uint32_t)((c + RING) * 2048);
@@ -335,7 +290,7 @@ __device__ __forceinline__ bool nx_fwd_epi(const nxf4 (&acc)[2][3], int wave, in
     const int f0 = tl * 16 + 4 * (lane >> 4);
     const int nv = Nout - f0 < 0 ? 0 : (Nout - f0 > 4 ? 4 : Nout - f0);
     const nxf4 z = nx_sum(acc[j]);
-    if (SAVE && row < rows_live && !(DPAC_NX_ABLATE & 2)) {
+    if (SAVE && row < rows_live) {
       float* zp = zrow0 + row * ztot + f0;
       if (nv == 4 && zvec) {
         *reinterpret_cast<nxf4*>(zp) = z;
@@ -363,9 +318,9 @@ __device__ __forceinline__ bool nx_fwd_epi(const nxf4 (&acc)[2][3], int wave, in
         bl[4 * j + e] = l[e];
       }
     } else {
-      bad |= nx_put4(out, kNxLd, row, f0, y, lane);
+      bad |= nx_put4(out, kNxLd, row, f0, y);
     }
-    if constexpr (MASK && !(DPAC_NX_ABLATE & 2)) {
+    if constexpr (MASK) {
       const uint32_t w = nx_quad_gather(nib, lane);
       if (mrow) mtile[64 * tl + nx_mask_idx(lane)] = (uint8_t)nx_pick4(w, lane & 3);
     }
@@ -397,7 +352,7 @@ __device__ __forceinline__ bool nx_bwd_epi(const nxf4 (&acc)[2][3], int wave, in
     const uint32_t w = nx_quad_gather(mb[j], lane);
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = e < nv ? v[e] * (((w >> (4 * e + i)) & 1u) ? 2.f : 1.f) : 0.f;
-    if (row < rows_live && !(DPAC_NX_ABLATE & 2)) {
+    if (row < rows_live) {
       const nxf4 gv = v * ri;  // exact: a power of two
       float* gp = grow0 + row * gtot + f0;
       if (nv == 4 && gvec) {
@@ -417,7 +372,7 @@ __device__ __forceinline__ bool nx_bwd_epi(const nxf4 (&acc)[2][3], int wave, in
         bl[4 * j + e] = l[e];
       }
     } else {
-      bad |= nx_put4(out, kNxLd, row, f0, v, lane);
+      bad |= nx_put4(out, kNxLd, row, f0, v);
     }
   }
   if constexpr (FOLD) nx_fold_prod(*fh, *fl, bh, bl, part, wave, lane);
@@ -496,9 +451,8 @@ __global__ __launch_bounds__(kNnThreads) void k_rollout_nn_x3(const E eq, const 
   const __amdgpu_buffer_rsrc_t rs_dw = make_rsrc(a.dw, slab * (uint32_t)a.N);
   const __amdgpu_buffer_rsrc_t rs_u = make_rsrc(a.u, a.u ? slab_u * (uint32_t)a.N : 0u);
   const int L = mlp.L, c_out = mlp.width[L + 1];
-  const int nch_out = (mlp.width[L] + 31) / 32;  // split-K: wave w < nch_out multiplies chunk w
-  constexpr bool kFold = DPAC_NX_FOLD != 0;
-  const int nparts = kFold ? kNnWaves : nch_out;  // split-K partials the step lanes add
+  const int nch_out = (mlp.width[L] + 31) / 32;  // 32-k chunks of the output layer's weight image
+  constexpr int nparts = kNnWaves;  // split-K partials the step lanes add: one per wave (nx_fold_prod)
   int zalign = mlp.ztot;  // 16-byte z saves where every hidden block starts 4-aligned
   for (int h = 1; h <= L; ++h) zalign |= mlp.zoff[h];
   const bool zvec = (zalign & 3) == 0;
@@ -532,10 +486,7 @@ __global__ __launch_bounds__(kNnThreads) void k_rollout_nn_x3(const E eq, const 
   // weights: the narrow products' for the whole launch, the first wide layer's
   nxh8 rih[1][2], ril[1][2], roh[1][2], rol[1][2], wh[kNxRing][2], wl[kNxRing][2];
   nx_loadw<1>(rih, ril, mlp.wx3[0], mlp.width[1], 1, 0, wave, wave + 8, lane);
-  if constexpr (kFold)
-    nx_fold_w(roh[0], rol[0], mlp.wx3[L], c_out, nch_out, wave, lane);  // the output layer, folded
-  else
-    nx_loadw<1>(roh, rol, mlp.wx3[L], c_out, nch_out, wave, 0, 1, lane);
+  nx_fold_w(roh[0], rol[0], mlp.wx3[L], c_out, nch_out, wave, lane);  // the output layer, folded
   if (L >= 2) nx_loadw<kNxRing>(wh, wl, mlp.wx3[1], mlp.width[2], kNxWide, 0, wave, wave + 8, lane);
 
   auto write_a0 = [&](const T (&xv)[M]) {  // addcmul(beta0, x, gamma0/sqrt(1+eps)), solver.py:265
@@ -563,8 +514,8 @@ __global__ __launch_bounds__(kNnThreads) void k_rollout_nn_x3(const E eq, const 
     {  // hidden layer 1 from a0 (narrow K, resident weights)
       nxf4 acc[2][3];
       nx_prod<1, kNxLd0, 0>(in0, 0, rih, ril, acc, lane);
-      if (kFold && L == 1)
-        bad |= nx_fwd_epi<SAVE, MASK, kFold>(acc, wave, lane, mlp.width[1], s_bn, img(0),
+      if (L == 1)
+        bad |= nx_fwd_epi<SAVE, MASK, true>(acc, wave, lane, mlp.width[1], s_bn, img(0),
                                              SAVE ? a.save_z + rowt * mlp.ztot + mlp.zoff[1] : nullptr, mlp.ztot,
                                              zvec, rows_live, mt, mrow, &roh[0], &rol[0], part);
       else
@@ -585,8 +536,8 @@ __global__ __launch_bounds__(kNnThreads) void k_rollout_nn_x3(const E eq, const 
 #endif
       const int ln = l + 1 < L ? l + 1 : 1;  // the next wide layer (this step's or the next one's first)
       nx_loadw<kNxRing>(wh, wl, mlp.wx3[ln], mlp.width[ln + 1], kNxWide, 0, wave, wave + 8, lane);
-      if (kFold && l + 1 == L)  // the last hidden layer: the output layer in its epilogue
-        bad |= nx_fwd_epi<SAVE, MASK, kFold>(acc, wave, lane, mlp.width[l + 1], s_bn + l * kNxBnLd, img(l),
+      if (l + 1 == L)  // the last hidden layer: the output layer in its epilogue
+        bad |= nx_fwd_epi<SAVE, MASK, true>(acc, wave, lane, mlp.width[l + 1], s_bn + l * kNxBnLd, img(l),
                                              SAVE ? a.save_z + rowt * mlp.ztot + mlp.zoff[l + 1] : nullptr,
                                              mlp.ztot, zvec, rows_live, MASK ? mt + 13 * 64 * l : nullptr, mrow,
                                              &roh[0], &rol[0], part);
@@ -597,19 +548,6 @@ __global__ __launch_bounds__(kNnThreads) void k_rollout_nn_x3(const E eq, const 
       NN_MARK(t, 1 + 2 * l);
       __syncthreads();
       NN_MARK(t, 2 + 2 * l);
-    }
-    if (!kFold) {
-      if (wave < nch_out) {  // output layer: chunk `wave` of hidden layer L for both output tiles
-        nxf4 acc[2][3];
-        nx_prod<1, kNxLd, 0>(img(L - 1), wave, roh, rol, acc, lane);
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          *reinterpret_cast<nxf4*>(part + (wave * 16 + (lane & 15)) * kNxPartLd + 16 * j + 4 * (lane >> 4)) =
-              nx_sum(acc[j]);
-      }
-      NN_MARK(t, 1 + 2 * L);
-      __syncthreads();
-      NN_MARK(t, 2 + 2 * L);
     }
     if (!stepper) return;
     // ---- u_t from the partials (fixed wave order), then the transition (step lanes) ----
@@ -713,9 +651,8 @@ __global__ __launch_bounds__(kNnThreads) void k_rollout_nn_bwd_x3(const E eq, co
   const Own<D, P> own(lc.p);
   const Own<CD, P> ownu(lc.p);
   const int L = mlp.L;
-  const int nch0 = (mlp.width[1] + 31) / 32;  // split-K of the product into a_0's gradient
-  constexpr bool kFold = DPAC_NX_FOLD != 0;
-  const int nparts = kFold ? kNnWaves : nch0;  // split-K partials the step lanes add
+  const int nch0 = (mlp.width[1] + 31) / 32;  // 32-k chunks of the weight image of the product into a_0's gradient
+  constexpr int nparts = kNnWaves;  // split-K partials the step lanes add: one per wave (nx_fold_prod)
   int galign = a.gtot;  // 16-byte G stores where every hidden block starts 4-aligned
   for (int h = 1; h <= L; ++h) galign |= a.goff[h];
   const bool gvec = (galign & 3) == 0;
@@ -744,10 +681,7 @@ __global__ __launch_bounds__(kNnThreads) void k_rollout_nn_bwd_x3(const E eq, co
   // weights of the transposed chain (weight_t_x3[i]: [width[i]][ceil(width[i+1] / 32)][64])
   nxh8 rih[1][2], ril[1][2], roh[1][2], rol[1][2], wh[kNxRing][2], wl[kNxRing][2];
   nx_loadw<1>(rih, ril, a.wtx3[L], mlp.width[L], 1, 0, wave, wave + 8, lane);
-  if constexpr (kFold)
-    nx_fold_w(roh[0], rol[0], a.wtx3[0], mlp.width[0], nch0, wave, lane);  // a_0's gradient, folded
-  else
-    nx_loadw<1>(roh, rol, a.wtx3[0], mlp.width[0], nch0, wave, 0, 1, lane);
+  nx_fold_w(roh[0], rol[0], a.wtx3[0], mlp.width[0], nch0, wave, lane);  // a_0's gradient, folded
   if (L >= 2) nx_loadw<kNxRing>(wh, wl, a.wtx3[L - 1], mlp.width[L - 1], kNxWide, 0, wave, wave + 8, lane);
   if (a.g_xN && stepper) own.load_masked(a.g_xN + lc.b * D, lam);
   T gD = (a.g_disc && stepper) ? a.g_disc[lc.b] : T(0);
@@ -850,8 +784,8 @@ __global__ __launch_bounds__(kNnThreads) void k_rollout_nn_bwd_x3(const E eq, co
     {  // hidden layer L from the output's gradient (narrow K, resident weights)
       nxf4 acc[2][3];
       nx_prod<1, kNxLd0, 0>(in0, 0, rih, ril, acc, lane);
-      if (kFold && L == 1)
-        bad |= nx_bwd_epi<kFold>(acc, wave, lane, mlp.width[L], mb[L - 1], img(0),
+      if (L == 1)
+        bad |= nx_bwd_epi<true>(acc, wave, lane, mlp.width[L], mb[L - 1], img(0),
                                  a.G + (rowt + row0) * a.gtot + a.goff[L], a.gtot, gvec, rows_live, ri, &roh[0],
                                  &rol[0], part);
       else
@@ -871,8 +805,8 @@ __global__ __launch_bounds__(kNnThreads) void k_rollout_nn_bwd_x3(const E eq, co
 #endif
       const int ln = l - 1 >= 1 ? l - 1 : L - 1;  // the next wide layer (this step's or the next one's first)
       nx_loadw<kNxRing>(wh, wl, a.wtx3[ln], mlp.width[ln], kNxWide, 0, wave, wave + 8, lane);
-      if (kFold && l == 1)  // hidden layer 1: the product into a_0's gradient in its epilogue
-        bad |= nx_bwd_epi<kFold>(acc, wave, lane, mlp.width[l], mb[l - 1], img(L - l),
+      if (l == 1)  // hidden layer 1: the product into a_0's gradient in its epilogue
+        bad |= nx_bwd_epi<true>(acc, wave, lane, mlp.width[l], mb[l - 1], img(L - l),
                                  a.G + (rowt + row0) * a.gtot + a.goff[l], a.gtot, gvec, rows_live, ri, &roh[0],
                                  &rol[0], part);
       else
@@ -881,19 +815,6 @@ __global__ __launch_bounds__(kNnThreads) void k_rollout_nn_bwd_x3(const E eq, co
       NN_MARK(t, 3 + 2 * (L - l));
       __syncthreads();
       NN_MARK(t, 4 + 2 * (L - l));
-    }
-    if (!kFold) {
-      if (wave < nch0) {  // dL/d a_0: chunk `wave` of hidden layer 1's gradient for both tiles
-        nxf4 acc[2][3];
-        nx_prod<1, kNxLd, 0>(img(L - 1), wave, roh, rol, acc, lane);
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          *reinterpret_cast<nxf4*>(part + (wave * 16 + (lane & 15)) * kNxPartLd + 16 * j + 4 * (lane >> 4)) =
-              nx_sum(acc[j]);
-      }
-      NN_MARK(t, 3 + 2 * L);
-      __syncthreads();
-      NN_MARK(t, 4 + 2 * L);
     }
     if (stepper) {  // G_0 and dL/dx_t = direct part + G_0 * s_0 (a_0 = beta_0 + x * s_0)
       const float* pr = part + g * kNxPartLd;
