@@ -27,6 +27,12 @@
 #ifndef DPAC_ST_TIGHT_CHUNKS
 #define DPAC_ST_TIGHT_CHUNKS 3  // hand-off chunks of a ring of 16-byte-aligned slots
 #endif
+#ifndef DPAC_ST_CHEAP_CHUNKS
+// chunks, from the horizon's start, that the loader issues through its cheap path (st_issue_chunk);
+// 2 is what the first hand-off needs (chunk 0 is published once chunk 1 is issued); a large value
+// (timing knob) issues every whole chunk that way
+#define DPAC_ST_CHEAP_CHUNKS 2
+#endif
 #ifndef DPAC_ST_PREFETCH
 // compute waves: 1 a whole chunk's dw read into registers at the chunk's top and an unrolled
 // remainder, where the instantiation takes it (kChunkRegs, below); 0 (timing knob) every
@@ -35,6 +41,8 @@
 #endif
 constexpr int kStCW = 4;   // compute wavefronts per workgroup
 constexpr int kStCH = 16;  // steps per hand-off chunk
+constexpr int kStCheapChunks = DPAC_ST_CHEAP_CHUNKS < 4096 ? DPAC_ST_CHEAP_CHUNKS : 4096;
+static_assert(kStCheapChunks >= 0, "DPAC_ST_CHEAP_CHUNKS counts chunks");
 constexpr int kStPrefetch = DPAC_ST_PREFETCH;
 static_assert(kStPrefetch == 0 || kStPrefetch == 1, "DPAC_ST_PREFETCH is 0 or 1");
 template <typename T, int D, int P>
@@ -58,7 +66,15 @@ struct StagedPlan {
   static constexpr int PADOFF = SLOT_LDS - 16;                 // where empty lanes read 0
   static constexpr int RS = CHUNKS * kStCH;
   static_assert(P < 4 || (SLOT % 16 == 0 && (PIECES - 1) * 1024 + 16 <= SLOT), "DMA pieces stay inside the slot");
+  // the loader's cheap issue path: a step's pieces before the last are whole (64 lanes x 16
+  // bytes), the last has kLastLanes lanes, and a piece is addressed by the instruction's
+  // immediate offset (12 bits unsigned at least, for the global and the LDS address alike)
+  static constexpr int kLastLanes = (SLOT - (PIECES - 1) * 1024) / 16;
+  static_assert(P < 4 || SLOT % 16 == 0, "a step's rows are whole 16-byte lane pieces");
+  static_assert(P < 4 || (kLastLanes >= 1 && kLastLanes <= 64), "the last piece has 1 .. 64 lanes");
+  static_assert(P < 4 || ((PIECES - 1) * 1024 + kLastLanes * 16 == SLOT), "the pieces cover the slot exactly");
   static constexpr bool kOk = P >= 4 && RS * SLOT_LDS <= kLdsCap && kStCH * PIECES <= 62;
+  static_assert(!kOk || (PIECES - 1) * 1024 < (1 << 12), "a piece's offset fits the immediate field");
 };
 
 template <class Fn, int... S>
@@ -110,6 +126,41 @@ __device__ __forceinline__ void st_wait_published(const int* s_ready, int want) 
     __builtin_amdgcn_s_sleep(1);
   }
 }
+
+// The loader's cheap issue of one chunk: NL 1 KB DMA pieces of each of the chunk's kStCH steps,
+// at byte offsets OFF0 + j * 1024 of the step's rows and of its slot (the instruction's immediate
+// offset applies to the global and to the LDS address alike).  g is the lane's source address in
+// the chunk's first step, slot the LDS address of the chunk's first slot (a chunk's slots are
+// contiguous: RS is a multiple of kStCH).  The loader is a lone wavefront and issue-bound, about
+// 4.5 cycles per instruction, so a piece costs what its address arithmetic costs: here a step is
+// one add on m0, one 64-bit add on the address and its loads, in ONE statement, which saves and
+// restores m0 once (the compiler reserves m0 and knows nothing of the loads: it inserts no vmcnt
+// wait for them, which the counted publish relies on).  The VALU add between the write of m0 and
+// the load that reads it is the wait state that pair needs; the first step has an s_nop.
+// Every lane the caller leaves enabled reads 16 bytes per piece: the caller bounds them.
+#define DPAC_ST_LD1 "global_load_lds_dwordx4 %1, off offset:%5\n\t"
+#define DPAC_ST_LD2 DPAC_ST_LD1 "global_load_lds_dwordx4 %1, off offset:%6\n\t"
+#define DPAC_ST_ADV "s_add_u32 m0, m0, %4\n\tv_lshl_add_u64 %1, %1, 0, %3\n\t"
+#define DPAC_ST_X15(a) a a a a a a a a a a a a a a a
+#define DPAC_ST_CHUNK_ASM(LD)                                                                        \
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t" LD DPAC_ST_X15(DPAC_ST_ADV LD) \
+               "s_mov_b32 m0, %0"                                                                    \
+               : "=&s"(keep), "+v"(g)                                                                \
+               : "s"(slot), "s"(step_bytes), "n"(SLOT_LDS), "n"(OFF0), "n"(OFF0 + 1024)              \
+               : "memory", "scc")
+template <int NL, int OFF0, int SLOT_LDS>
+__device__ __forceinline__ void st_issue_chunk(uint64_t g, uint32_t slot, int64_t step_bytes) {
+  static_assert(kStCH == 16, "the statement is one step and 15 advances");
+  static_assert(NL >= 0 && NL <= 2 && OFF0 + (NL - 1) * 1024 < (1 << 12), "immediate offsets");
+  [[maybe_unused]] int keep;
+  if constexpr (NL == 1) DPAC_ST_CHUNK_ASM(DPAC_ST_LD1);
+  if constexpr (NL == 2) DPAC_ST_CHUNK_ASM(DPAC_ST_LD2);
+}
+#undef DPAC_ST_CHUNK_ASM
+#undef DPAC_ST_X15
+#undef DPAC_ST_ADV
+#undef DPAC_ST_LD2
+#undef DPAC_ST_LD1
 
 // Timing-only builds (-DDPAC_ST_TRACE=1, like DPAC_NN_TRACE): lane 0 of every wavefront of the
 // first and the last workgroup stores the shader clock (low 32 bits) at fixed points of
@@ -236,6 +287,21 @@ __global__ __launch_bounds__(64 * st_waves<GEN>()) void k_rollout_staged(const E
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)s_ring;
     const char* base = (const char*)(a.dw + row0 * D);
     const int64_t step_bytes = a.B * D * (int64_t)sizeof(T);
+    // A whole chunk of a full workgroup goes through st_issue_chunk: no bounds predicate, source
+    // and slot addresses advanced by step_bytes and SLOT_LDS per step.  Every step reads exactly
+    // the SLOT bytes of its rows: all lanes in the pieces before the last, kLastLanes lanes in
+    // the last, and the chunk's last pieces are issued together under one exec change (the
+    // counted wait counts instructions, in any order).  A partial workgroup and the horizon's
+    // last, clamped chunk take the predicated path below, which also issues PIECES instructions
+    // per step.
+    // Only the first kStCheapChunks chunks go that way: they are what the compute waves wait for
+    // at start-up.  From then on the loader is chunks ahead, and issuing a chunk in a burst (a
+    // third of the cycles) made the compute waves' steady state slower by more than the start-up
+    // gained, so later chunks keep the slower, evenly spaced issue.
+    const bool cheap = rows_live == TPW;
+    const int64_t chunk_bytes = step_bytes * kStCH;
+    uint64_t csrc = (uint64_t)(uintptr_t)base + (uint32_t)lane * 16u;  // this lane's 16 bytes of the chunk's first step
+    uint32_t cslot = lds0;                                             // the chunk's first slot: lds0 + (c0 % RS) * SLOT_LDS
     for (int c0 = 0; c0 < N; c0 += kStCH) {
       // the slots of this chunk were last read at steps c0 + s - RS: wait for every consumer
       const int need = c0 + kStCH - RS;
@@ -244,22 +310,29 @@ __global__ __launch_bounds__(64 * st_waves<GEN>()) void k_rollout_staged(const E
 #if DPAC_ST_TRACE
       ST_MARK(ST_CHUNK(16, c0));
 #endif
+      if (cheap && c0 < kStCheapChunks * kStCH && c0 + kStCH <= N) {
+        st_issue_chunk<PIECES - 1, 0, SLOT_LDS>(csrc, cslot, step_bytes);
+        if (lane < PL::kLastLanes) st_issue_chunk<1, (PIECES - 1) * 1024, SLOT_LDS>(csrc, cslot, step_bytes);
+        csrc += chunk_bytes;
+        cslot = cslot + kStCH * SLOT_LDS == lds0 + RS * SLOT_LDS ? lds0 : cslot + kStCH * SLOT_LDS;
+      } else {
 #pragma unroll
-      for (int s = 0; s < kStCH; ++s) {
-        const int t = c0 + s < N ? c0 + s : N - 1;  // past the end: re-copy the last step (unused)
-        const char* src = base + t * step_bytes;
-        const uint32_t slot = lds0 + (uint32_t)((t % RS) * SLOT_LDS);
+        for (int s = 0; s < kStCH; ++s) {
+          const int t = c0 + s < N ? c0 + s : N - 1;  // past the end: re-copy the last step (unused)
+          const char* src = base + t * step_bytes;
+          const uint32_t slot = lds0 + (uint32_t)((t % RS) * SLOT_LDS);
 #pragma unroll
-        for (int k = 0; k < PIECES; ++k) {
-          const uint32_t off = (uint32_t)((k * 64 + lane) * 16);
-          const char* gp = src + (off < bytes ? off : 0u);  // lane 0 past the rows re-reads row 0
-          const uint32_t m0 = __builtin_amdgcn_readfirstlane(slot + (uint32_t)(k * 1024));
-          // lanes past the rows write nothing (the zero pad stays zero); lane 0 always issues,
-          // so every instruction counts in vmcnt (it lands at k*1024, never on the pad)
-          if (off < bytes || lane == 0) {
-            int keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(gp), "s"(m0) : "memory");
+          for (int k = 0; k < PIECES; ++k) {
+            const uint32_t off = (uint32_t)((k * 64 + lane) * 16);
+            const char* gp = src + (off < bytes ? off : 0u);  // lane 0 past the rows re-reads row 0
+            const uint32_t m0 = __builtin_amdgcn_readfirstlane(slot + (uint32_t)(k * 1024));
+            // lanes past the rows write nothing (the zero pad stays zero); lane 0 always issues,
+            // so every instruction counts in vmcnt (it lands at k*1024, never on the pad)
+            if (off < bytes || lane == 0) {
+              int keep;
+              asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                           : "=&s"(keep) : "v"(gp), "s"(m0) : "memory");
+            }
           }
         }
       }
