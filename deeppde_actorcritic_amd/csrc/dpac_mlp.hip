@@ -2,7 +2,6 @@
 // gradients over independent rows, dpac_mlp_grad.h), compiled once for both
 // dtypes.  Argument checking and error strings live in dpac_abi.hip.
 #include <algorithm>
-
 #include <cstdlib>
 
 #include "dpac_host.h"
@@ -22,7 +21,7 @@ PgArgs<T> pg_args(const dpac_mlp& net, int64_t rows, const void* x, int64_t ldx,
   const int L = net.n_hidden;
   a.rows = rows;
   a.L = L;
-  int zt = 0, gt = 0, sw = 0;
+  int zt = 0, gt = 0;
   for (int i = 0; i <= L + 1; ++i) {
     a.width[i] = net.width[i];
     a.scale[i] = (const T*)net.bn_scale[i];
@@ -31,7 +30,6 @@ PgArgs<T> pg_args(const dpac_mlp& net, int64_t rows, const void* x, int64_t ldx,
     if (i > 0) zt += net.width[i];
     a.goff[i] = gt;
     gt += net.width[i];
-    sw += net.width[i];
   }
   a.bias = (const T*)net.bias;
   a.x = (const T*)x;
@@ -45,33 +43,25 @@ PgArgs<T> pg_args(const dpac_mlp& net, int64_t rows, const void* x, int64_t ldx,
   for (int i = 0; i <= L + 1; ++i) { a.off_beta[i] = o; o += net.width[i]; }
   for (int i = 0; i <= L; ++i) { a.off_W[i] = o; o += (int64_t)net.width[i] * net.width[i + 1]; }
   a.ptot = o;
-  (void)sw;
   return a;
 }
 
-#ifndef DPAC_PG_CHUNKS
-#define DPAC_PG_CHUNKS 256  // 2 workgroups per CU on the wide layers (measured 819 -> 681 us at 204800 rows)
-#endif
-#ifndef DPAC_PG_MIN_ROWS
-#define DPAC_PG_MIN_ROWS 256  // rows per chunk at least: small row counts (the critic's V over 3B rows)
-#endif                        // would otherwise write and re-read ~256 near-empty partials
-// DPAC_PG_MIN_ROWS in the environment overrides the floor (timing comparisons; read per call, so
-// a process must keep one value between sizing its workspace and launching)
-inline int64_t pg_min_rows() {
-  const char* e = getenv("DPAC_PG_MIN_ROWS");
-  const long long v = e ? atoll(e) : 0;
-  return v >= 16 ? (int64_t)v : (int64_t)DPAC_PG_MIN_ROWS;
-}
+// 256 chunks: 2 workgroups per CU on the wide layers (measured 819 -> 681 us at 204 800 rows)
+constexpr int64_t kPgChunks = 256;
+// rows per chunk at least: small row counts (the critic's V over 3B rows) would otherwise write and
+// re-read ~256 near-empty partials (measured: 64 / 32 rows take the iteration 3.49 -> 3.51 / 3.70 ms).
+// One constant for sizing the workspace and for launching.
+constexpr int64_t kPgMinRows = 256;
 
 template <typename T>
 int64_t pg_chunk_rows(int64_t rows, int64_t max_ld) {
-  // DPAC_PG_CHUNKS chunks of at least DPAC_PG_MIN_ROWS rows: the wide layers' two column
+  // kPgChunks chunks of at least kPgMinRows rows: the wide layers' two column
   // groups give 2 workgroups per CU, the narrow ones one, and a partial buffer the reduce
   // reads in ~25 us.  A chunk's rows are addressed through 32-bit buffer descriptors: keep
   // them below 2 GiB.
   constexpr int SR = PgCfg<T>::SR;
-  int64_t per = (rows + DPAC_PG_CHUNKS - 1) / DPAC_PG_CHUNKS;
-  per = std::max<int64_t>(per, pg_min_rows());
+  int64_t per = (rows + kPgChunks - 1) / kPgChunks;
+  per = std::max<int64_t>(per, kPgMinRows);
   const int64_t cap = (((int64_t)1 << 31) - 1) / (max_ld * (int64_t)sizeof(T)) / SR * SR;
   per = (per + SR - 1) / SR * SR;
   return std::max<int64_t>(std::min(per, cap), SR);
@@ -88,33 +78,6 @@ int64_t ws_bytes(int64_t rows, const dpac_mlp& net) {
   const int64_t per = pg_chunk_rows<T>(rows, max_ld(a));
   const int64_t nch = (rows + per - 1) / per;
   return nch * a.ptot * (int64_t)sizeof(T);
-}
-
-#ifndef DPAC_PG_FORK
-#define DPAC_PG_FORK 0  // narrow layers' launches on a forked stream beside the wide ones
-#endif
-// The fork: a per-device auxiliary stream and two events, created on first use (outside
-// any capture: dpac_mlp_param_grads_workspace, which every caller runs first, creates
-// them).  Inside a stream capture the event record / wait pair becomes graph edges, so
-// the narrow layers are a parallel branch of the captured graph.
-struct PgFork {
-  hipStream_t aux = nullptr;
-  hipEvent_t fork = nullptr, join = nullptr;
-};
-PgFork* pg_fork() {
-  static PgFork f[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-  PgFork& r = f[dev];
-  if (!r.aux) {
-    if (hipStreamCreateWithFlags(&r.aux, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&r.fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&r.join, hipEventDisableTiming) != hipSuccess) {
-      r.aux = nullptr;
-      return nullptr;
-    }
-  }
-  return &r;
 }
 
 // one layer of the f32 / f64 kernel (k_param_grads): the wave grid and the tile counts are
@@ -164,9 +127,9 @@ inline bool pg_x3(const dpac_mlp& net) {
   return true;
 }
 
-// one split-fp16 launch (dynamic LDS: the plan's size)
-template <int NTI, int NTJ, int WI, bool L0, int NW = kPgxWaves>
-int pgx_launch(const PgArgs<float>& a, int l, dim3 grid, hipStream_t s) {
+// one split-fp16 launch of the plan's kernel (dynamic LDS: the plan's size)
+template <int NTI, int NTJ, int WI, bool L0, int NW>
+int pgx_launch(PgxPlan<NTI, NTJ, WI, L0, NW>, const PgArgs<float>& a, int l, dim3 grid, hipStream_t s) {
   using PL = PgxPlan<NTI, NTJ, WI, L0, NW>;
   auto k = k_param_grads_x3<NTI, NTJ, WI, L0, NW>;
   if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
@@ -175,7 +138,6 @@ int pgx_launch(const PgArgs<float>& a, int l, dim3 grid, hipStream_t s) {
   hipLaunchKernelGGL(k, grid, dim3(PL::kThreads), PL::kSmem, s, a, l);
   return (int)hipGetLastError();
 }
-
 
 // The merged-group kernel (k_param_grads_x3w: one 256-column group, A read once per chunk) for
 // the wide hidden layers and for the input layer into a wide layer: rows of A, z_{l+1} (and G_0
@@ -194,105 +156,26 @@ inline bool pgx_w_ok(const PgArgs<float>& a, int l) {
   return K > 32 && H > 32 && K <= 208 && K % 4 == 0 && a.zoff[l] % 4 == 0 && out;
 }
 
-// Layer l >= 1 on the merged-group kernel's 13-tile bin: a wide hidden layer (pgx_w_ok), or the
-// output layer of <= 32 columns (one launch with the wide layers before it; its 16 waves then
-// hold 2 column tiles, the others idle) — both with 129..208 inputs.
-inline bool pgw13_ok(const PgArgs<float>& a, int l) {
-  const int K = a.width[l], H = a.width[l + 1];
-  if (K <= 128 || K > 208 || K % 4 != 0 || a.zoff[l] % 4 != 0) return false;
-  if (pgx_w_ok(a, l)) return true;
-  // the output layer joins only with DPAC_PG_MERGE_OUT=1: on the merged-group kernel it is slower
-  // than on its own 8-wavefront kernel (round 5: all layers 467 vs 447 us at 204 800 rows)
-  const char* e = getenv("DPAC_PG_MERGE_OUT");
-  return l == a.L && H <= 32 && H % 4 == 0 && a.ztot % 4 == 0 && a.zoff[l + 1] % 4 == 0 &&
-         (reinterpret_cast<uintptr_t>(a.z) & 15) == 0 && e && e[0] == '1';
-}
-
-static_assert(PgwPlan<13>::kSmem + kPgwRawG0c <= 160 * 1024, "a merged launch from the input layer fits the LDS");
-
 // DPAC_PG_MERGE=0: every layer its own launch (timing comparisons; bitwise the same results)
 inline bool pg_merge() {
   const char* e = getenv("DPAC_PG_MERGE");  // read per launch
   return !(e && e[0] == '0');
 }
-// DPAC_PG_MERGE_IN=1: the input layer in the merged launch too (k_param_grads_x3w MODE 2).  Off
-// by default: the run-time input-layer state makes that instantiation spill 54 VGPRs (round 5).
-inline bool pg_merge_in() {
-  const char* e = getenv("DPAC_PG_MERGE_IN");  // read per launch
-  return pg_merge() && e && e[0] == '1';
-}
 
 template <int NTI, bool L0 = false, int MODE = 0>
-int pgw_launch(const PgArgs<float>& a, int l, int64_t nch, hipStream_t s, int extra_lds = 0) {
+int pgw_launch(const PgArgs<float>& a, int l, int64_t nch, hipStream_t s) {
   using PL = PgwPlan<NTI, L0>;
   auto k = k_param_grads_x3w<NTI, L0, MODE>;
-  const int lds = PL::kSmem + extra_lds;  // + the merged input layer's compact G_0 slots
-  if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, lds))
-    return (int)e;
-  hipLaunchKernelGGL(k, dim3((unsigned)nch), dim3(kPgwThreads), lds, s, a, l);
-  return (int)hipGetLastError();
-}
-
-#ifndef DPAC_PGW_DEFAULT_D
-#define DPAC_PGW_DEFAULT_D 0  // k_param_grads_x3d by default (DPAC_PGW_KERNEL overrides)
-#endif
-// DPAC_PGW_KERNEL=w: the 16-wavefront merged-group kernel (k_param_grads_x3w, rounds 4-5); d: its
-// double-buffered 8-wavefront form (k_param_grads_x3d, round 6), bitwise the same results.
-inline bool pg_double() {
-  const char* e = getenv("DPAC_PGW_KERNEL");  // read per launch
-  return e ? e[0] == 'd' : DPAC_PGW_DEFAULT_D;
-}
-
-template <int NTI, bool L0 = false, int MODE = 0>
-int pgd_launch(const PgArgs<float>& a, int l, int64_t nch, hipStream_t s) {
-  using PL = PgdPlan<NTI, L0>;
-  auto k = k_param_grads_x3d<NTI, L0, MODE>;
   if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, PL::kSmem))
     return (int)e;
-  hipLaunchKernelGGL(k, dim3((unsigned)nch), dim3(kPgdThreads), PL::kSmem, s, a, l);
+  hipLaunchKernelGGL(k, dim3((unsigned)nch), dim3(kPgwThreads), PL::kSmem, s, a, l);
   return (int)hipGetLastError();
 }
 
-// one layer of the split-fp16 kernel: the wide hidden layers and the input layer one 256-column
-// group of 16 waves (pgx_w_ok), other wide outputs 1 x 8 waves (one column tile each,
-// 128-column groups), outputs of <= 32 columns 8 x 1 waves over the row tiles
-int launch_x3_layer(const PgArgs<float>& a, int l, int64_t nch, hipStream_t s) {
-  const int K = a.width[l], H = a.width[l + 1];
-  const int nti = (K + 15) / 16;
-  if (pgx_w_ok(a, l) && pg_double()) {
-    if (l == 0) return nti <= 1 ? pgd_launch<1, true>(a, l, nch, s) : pgd_launch<2, true>(a, l, nch, s);
-    if (nti <= 4) return pgd_launch<4>(a, l, nch, s);
-    if (nti <= 8) return pgd_launch<8>(a, l, nch, s);
-    return pgd_launch<13>(a, l, nch, s);
-  }
-  if (pgx_w_ok(a, l)) {
-    if (l == 0) return nti <= 1 ? pgw_launch<1, true>(a, l, nch, s) : pgw_launch<2, true>(a, l, nch, s);
-    if (nti <= 4) return pgw_launch<4>(a, l, nch, s);
-    if (nti <= 8) return pgw_launch<8>(a, l, nch, s);
-    return pgw_launch<13>(a, l, nch, s);  // K <= 208 (13 tiles: 128 VGPRs without spills in the loop)
-  }
-  if (H <= 32) {
-    const int ntj = (H + 15) / 16, nt8 = (nti + 7) / 8;
-    const dim3 grid((unsigned)nch, 1u);
-    if (nt8 <= 1) return ntj == 1 ? pgx_launch<1, 1, 8, false>(a, l, grid, s) : pgx_launch<1, 2, 8, false>(a, l, grid, s);
-    return ntj == 1 ? pgx_launch<2, 1, 8, false>(a, l, grid, s) : pgx_launch<2, 2, 8, false>(a, l, grid, s);
-  }
-  if (l == 0) {  // the input layer (d <= 32: launch() sends the others to the f32 kernel)
-    const dim3 grid((unsigned)nch, (unsigned)((H + 127) / 128));
-    return nti <= 1 ? pgx_launch<1, 1, 1, true>(a, l, grid, s) : pgx_launch<2, 1, 1, true>(a, l, grid, s);
-  }
-  const dim3 grid((unsigned)nch, (unsigned)((H + 127) / 128));
-  if (nti <= 1) return pgx_launch<1, 1, 1, false>(a, l, grid, s);
-  if (nti <= 2) return pgx_launch<2, 1, 1, false>(a, l, grid, s);
-  if (nti <= 4) return pgx_launch<4, 1, 1, false>(a, l, grid, s);
-  if (nti <= 8) return pgx_launch<8, 1, 1, false>(a, l, grid, s);
-  return pgx_launch<13, 1, 1, false>(a, l, grid, s);
-}
-
-// The configuration launch_x3_layer gives layer l off the merged-group kernels (pgx_w_ok false)
-// and its column groups, as a k_param_grads_x3_seg segment
+// The 8-wavefront kernel's configuration for layer l and its column groups (also a
+// k_param_grads_x3_seg segment): outputs of <= 32 columns 8 x 1 waves over the row tiles, other
+// outputs 1 x 8 waves (one column tile each, 128-column groups); input tiles in bins
 inline int x3_layer_cfg(const PgArgs<float>& a, int l, int& ngrp) {
   const int K = a.width[l], H = a.width[l + 1];
   const int nti = (K + 15) / 16;
@@ -303,6 +186,7 @@ inline int x3_layer_cfg(const PgArgs<float>& a, int l, int& ngrp) {
     return ntj == 1 ? kPgxN21 : kPgxN22;
   }
   ngrp = (H + 127) / 128;
+  // the input layer (d <= 32: launch() sends the others to the f32 kernel)
   if (l == 0) return nti <= 1 ? kPgxIn1 : kPgxIn2;
   if (nti <= 1) return kPgxW1;
   if (nti <= 2) return kPgxW2;
@@ -311,9 +195,37 @@ inline int x3_layer_cfg(const PgArgs<float>& a, int l, int& ngrp) {
   return kPgxW13;
 }
 
-#ifndef DPAC_PG_SEG_MAX_BLOCKS
-#define DPAC_PG_SEG_MAX_BLOCKS 1024  // every layer in one launch up to this many workgroups in all
-#endif
+// one layer of the split-fp16 kernel: the wide hidden layers and the input layer one 256-column
+// group of 16 waves (pgx_w_ok), every other layer the 8-wavefront kernel (x3_layer_cfg)
+int launch_x3_layer(const PgArgs<float>& a, int l, int64_t nch, hipStream_t s) {
+  if (pgx_w_ok(a, l)) {
+    const int nti = (a.width[l] + 15) / 16;
+    if (l == 0) return nti <= 1 ? pgw_launch<1, true>(a, l, nch, s) : pgw_launch<2, true>(a, l, nch, s);
+    if (nti <= 4) return pgw_launch<4>(a, l, nch, s);
+    if (nti <= 8) return pgw_launch<8>(a, l, nch, s);
+    return pgw_launch<13>(a, l, nch, s);  // K <= 208 (13 tiles: 128 VGPRs without spills in the loop)
+  }
+  int ngrp = 1;
+  const int cfg = x3_layer_cfg(a, l, ngrp);
+  const dim3 grid((unsigned)nch, (unsigned)ngrp);
+  switch (cfg) {
+#define DPAC_PGX(CFG) case CFG: return pgx_launch(PgxCfgT<CFG>::PL{}, a, l, grid, s)
+    DPAC_PGX(kPgxIn1);
+    DPAC_PGX(kPgxIn2);
+    DPAC_PGX(kPgxW1);
+    DPAC_PGX(kPgxW2);
+    DPAC_PGX(kPgxW4);
+    DPAC_PGX(kPgxW8);
+    DPAC_PGX(kPgxW13);
+    DPAC_PGX(kPgxN11);
+    DPAC_PGX(kPgxN12);
+    DPAC_PGX(kPgxN21);
+    default: DPAC_PGX(kPgxN22);
+#undef DPAC_PGX
+  }
+}
+
+constexpr int64_t kPgSegMaxBlocks = 1024;  // every layer in one launch up to this many workgroups in all
 // Round 6: when every layer runs on the 8-wavefront split-fp16 kernel and their grids together
 // stay small (the critic's V network over 3 B rows: 168 workgroups), one k_param_grads_x3_seg
 // launch runs them side by side (measured per layer, the four launches were latency-bound:
@@ -337,7 +249,7 @@ inline bool pg_seg_build(const PgArgs<float>& a, int64_t nch, PgxSegs& sg, int& 
     b0 += nch * ngrp;
     smem = std::max(smem, pgx_cfg_smem(cfg));
   }
-  return b0 <= DPAC_PG_SEG_MAX_BLOCKS;
+  return b0 <= kPgSegMaxBlocks;
 }
 
 constexpr int64_t kFallbackBlocksPg = 256;  // the guarded f32 parameter-gradient fallback's grid
@@ -371,18 +283,13 @@ int launch(int64_t rows, const dpac_mlp& net, double gamma_scale, const void* x,
           if (hipError_t e = hipGetLastError()) return (int)e;
         }
         for (int l = 0; l <= a.L && !fb_only && !seg; ++l) {
-          // a run of adjacent layers of the merged-group kernel's 13-tile bin (the wide hidden
-          // layers, and the output layer after them): one launch (k_param_grads_x3w, lsel < 0)
-          // (and the input layer before them, run by the same kernel at run time)
-          const bool in = l == 0 && pg_merge_in() && pgx_w_ok(a, 0);
-          int nl = in ? 1 : 0;
-          while (pg_merge() && (l >= 1 || in) && l + nl <= a.L && pgw13_ok(a, l + nl)) ++nl;
+          // a run of adjacent wide hidden layers of the merged-group kernel's 13-tile bin (pgx_w_ok
+          // and 129..208 inputs): one launch (k_param_grads_x3w, lsel < 0)
+          int nl = 0;
+          while (pg_merge() && l >= 1 && l + nl <= a.L && pgx_w_ok(a, l + nl) && a.width[l + nl] > 128) ++nl;
           if (nl >= 2) {
             const int64_t g = (nch + 7) / 8 * 8 * nl;
-            if (int e = in ? pgw_launch<13, false, 2>(a, -(l + 8 * nl), g, s0, kPgwRawG0c)
-                           : (pg_double() ? pgd_launch<13, false, 1>(a, -(l + 8 * nl), g, s0)
-                                          : pgw_launch<13, false, 1>(a, -(l + 8 * nl), g, s0)))
-              return e;
+            if (int e = pgw_launch<13, false, 1>(a, -(l + 8 * nl), g, s0)) return e;
             l += nl - 1;
             continue;
           }
@@ -422,28 +329,8 @@ int launch(int64_t rows, const dpac_mlp& net, double gamma_scale, const void* x,
   if (net.guard_phase == DPAC_GUARD_FALLBACK_ONLY) return 0;  // phase 1 did the whole work
   a.part = (T*)ws;
   const int64_t nch = (rows + a.rows_per_chunk - 1) / a.rows_per_chunk;
-  // narrow layers (K or H <= 32: grids of 256-512 small workgroups) on the forked
-  // stream; every layer writes its own partial columns, so the branches share nothing
-  PgFork* fk = DPAC_PG_FORK ? pg_fork() : nullptr;
-  bool forked = false;
-  for (int l = 0; l <= a.L; ++l) {  // one launch per layer
-    const int K = a.width[l], H = a.width[l + 1];
-    hipStream_t s = s0;
-    if (fk && (K <= 32 || H <= 32)) {
-      if (!forked) {
-        if (hipError_t e = hipEventRecord(fk->fork, s0)) return (int)e;
-        if (hipError_t e = hipStreamWaitEvent(fk->aux, fk->fork, 0)) return (int)e;
-        forked = true;
-      }
-      s = fk->aux;
-    }
-    if (int e = launch_f32_layer<T>(a, l, nch, s)) return e;
-    if (hipError_t e = hipGetLastError()) return (int)e;
-  }
-  if (forked) {
-    if (hipError_t e = hipEventRecord(fk->join, fk->aux)) return (int)e;
-    if (hipError_t e = hipStreamWaitEvent(s0, fk->join, 0)) return (int)e;
-  }
+  for (int l = 0; l <= a.L; ++l)  // one launch per layer
+    if (int e = launch_f32_layer<T>(a, l, nch, s0)) return e;
   const int64_t n = a.ptot + a.width[a.L + 1];
   hipLaunchKernelGGL(k_param_grads_reduce<T>, dim3((unsigned)((n + kRedCols - 1) / kRedCols)), dim3(256), 0, s0,
                      a, (int)nch, (T)gamma_scale, (T*)out);
@@ -475,8 +362,9 @@ MrArgs<T> mr_args(const dpac_mlp& net, int64_t rows) {
   return a;
 }
 
-template <typename T>
-void set_td(MrArgs<T>& a, const TdRows* td) {
+// the TD1 operands into an MrArgs<T> or an X3Args (T = float)
+template <typename T, class A>
+void set_td(A& a, const TdRows* td) {
   if (!td) return;
   a.td_x = (const T*)td->x;
   a.td_ldx = td->ldx;
@@ -512,16 +400,7 @@ X3Args x3_args(const dpac_mlp& net, int64_t rows, const void* const* img, const 
   a.ztot = m.ztot;
   a.gtot = m.gtot;
   a.nblk = (rows + 63) / 64;  // the sign-bit mask's 64-row blocks
-  if (td) {
-    a.td_x = (const float*)td->x;
-    a.td_ldx = td->ldx;
-    a.td_u = (const float*)td->u;
-    a.td_ldu = td->ldu;
-    a.td_dw = (const float*)td->dw;
-    a.td_p = td->p;
-    a.td_sa = (float)td->sa;
-    a.td_sb = (float)td->sb;
-  }
+  set_td<float>(a, td);
   return a;
 }
 
@@ -544,7 +423,7 @@ int rows_fwd(int64_t rows, const dpac_mlp& net, const void* x, int64_t ldx, void
              void* save_z, const TdRows* td, uint8_t* mask, int32_t* written, hipStream_t s) {
   if (written) *written = 0;
   MrArgs<T> a = mr_args<T>(net, rows);
-  set_td(a, td);
+  set_td<T>(a, td);
   if (td) a.gdot = (T*)td->gdot;
   a.x = (const T*)x;
   a.ldx = ldx;
@@ -562,7 +441,7 @@ int rows_fwd(int64_t rows, const dpac_mlp& net, const void* x, int64_t ldx, void
       xa.out = (float*)out;
       xa.z = (float*)save_z;
       xa.status = net.status;
-      xa.mask = (save_z && kX3RT == 4) ? reinterpret_cast<uint32_t*>(mask) : nullptr;  // 64-row blocks
+      xa.mask = save_z ? reinterpret_cast<uint32_t*>(mask) : nullptr;  // 64-row blocks
       if (net.guard_phase != DPAC_GUARD_FALLBACK_ONLY)
         if (int e = x3_launch(k_mlp_rows_fwd_x3, xa, s)) return e;
       if (written && xa.mask) *written = 1;
@@ -578,9 +457,26 @@ int rows_fwd(int64_t rows, const dpac_mlp& net, const void* x, int64_t ldx, void
   return (int)hipGetLastError();
 }
 
+// the f32 / f64 row backward's arguments
+template <typename T>
+MrArgs<T> mr_bwd_args(int64_t rows, const dpac_mlp& net, const void* const* wt, const void* save_z,
+                      const void* g_out, void* G, void* g_x, const TdRows* td) {
+  MrArgs<T> a = mr_args<T>(net, rows);
+  set_td<T>(a, td);
+  if (td) a.g_gdot = (const T*)td->g_gdot;
+  for (int i = 0; i <= a.L; ++i) a.wt[i] = (const T*)wt[i];
+  a.z = (T*)save_z;
+  a.g_out = (const T*)g_out;
+  a.G = (T*)G;
+  a.g_x = (T*)g_x;
+  return a;
+}
+
 template <typename T>
 int rows_bwd(int64_t rows, const dpac_mlp& net, const void* const* wt, const void* save_z,
              const uint8_t* mask, const void* g_out, void* G, void* g_x, const TdRows* td, hipStream_t s) {
+  constexpr int ROWS = MrCfg<T>::RT * 16;
+  const int64_t nblk = (rows + ROWS - 1) / ROWS;
   if constexpr (std::is_same<T, float>::value) {
     if (x3_all(net, net.weight_t_x3) && (!net.status || x3_all(net, wt))) {
       X3Args a = x3_args(net, rows, net.weight_t_x3, td);
@@ -596,33 +492,17 @@ int rows_bwd(int64_t rows, const dpac_mlp& net, const void* const* wt, const voi
                          : x3_launch(k_mlp_rows_bwd_x3<false>, a, s, kX3RowsB, kX3LdsBytesB))
           return e;
       if (!net.status || net.guard_phase == DPAC_GUARD_SPLIT_ONLY) return 0;
-      MrArgs<T> f = mr_args<T>(net, rows);  // the f32 kernel, run only once the x3 kernel fell back
-      set_td(f, td);
-      if (td) f.g_gdot = (const T*)td->g_gdot;
-      for (int i = 0; i <= f.L; ++i) f.wt[i] = (const T*)wt[i];
-      f.z = (T*)save_z;
-      f.g_out = (const T*)g_out;
-      f.G = (T*)G;
-      f.g_x = (T*)g_x;
+      // the f32 kernel, run only once the x3 kernel fell back
+      MrArgs<T> f = mr_bwd_args<T>(rows, net, wt, save_z, g_out, G, g_x, td);
       f.guard = net.status;
-      constexpr int ROWS = MrCfg<T>::RT * 16;
-      hipLaunchKernelGGL(k_mlp_rows_bwd<T>, dim3((unsigned)std::min((rows + ROWS - 1) / ROWS, kFallbackBlocks)),
-                         dim3(kMrThreads), 0, s, f);
+      hipLaunchKernelGGL(k_mlp_rows_bwd<T>, dim3((unsigned)std::min(nblk, kFallbackBlocks)), dim3(kMrThreads), 0,
+                         s, f);
       return (int)hipGetLastError();
     }
   }
   if (net.guard_phase == DPAC_GUARD_FALLBACK_ONLY) return 0;  // phase 1 did the whole work
-  MrArgs<T> a = mr_args<T>(net, rows);
-  set_td(a, td);
-  if (td) a.g_gdot = (const T*)td->g_gdot;
-  for (int i = 0; i <= a.L; ++i) a.wt[i] = (const T*)wt[i];
-  a.z = (T*)save_z;
-  a.g_out = (const T*)g_out;
-  a.G = (T*)G;
-  a.g_x = (T*)g_x;
-  constexpr int ROWS = MrCfg<T>::RT * 16;
-  hipLaunchKernelGGL(k_mlp_rows_bwd<T>, dim3((unsigned)((rows + ROWS - 1) / ROWS)),
-                     dim3(kMrThreads), 0, s, a);
+  const MrArgs<T> a = mr_bwd_args<T>(rows, net, wt, save_z, g_out, G, g_x, td);
+  hipLaunchKernelGGL(k_mlp_rows_bwd<T>, dim3((unsigned)nblk), dim3(kMrThreads), 0, s, a);
   return (int)hipGetLastError();
 }
 
@@ -644,12 +524,11 @@ int mlp_rows_bwd_launch(int dtype, int64_t rows, const dpac_mlp& net, const void
 
 int64_t mlp_rows_mask_bytes(int dtype, int64_t rows, const dpac_mlp& net) {
   // only the split-fp16 forward writes it, over 64-row workgroups (dpac_mlp_x3.h X3Args::mask)
-  if (dtype != DPAC_F32 || !x3_all(net, net.weight_x3) || kX3RT != 4) return 0;
+  if (dtype != DPAC_F32 || !x3_all(net, net.weight_x3)) return 0;
   return (int64_t)net.n_hidden * ((rows + 63) / 64) * kX3MaskWords * 4;
 }
 
 int64_t mlp_param_grads_ws_bytes(int dtype, int64_t rows, const dpac_mlp& net) {
-  if (DPAC_PG_FORK) (void)pg_fork();
   return dtype == DPAC_F64 ? ws_bytes<double>(rows, net) : ws_bytes<float>(rows, net);
 }
 

@@ -44,18 +44,7 @@ typedef float pgf4 __attribute__((ext_vector_type(4)));
 constexpr int kPgxThreads = 512;
 constexpr int kPgxWaves = 8;
 constexpr int kPgxSR = 32;  // rows per sub-chunk = the MFMA's K
-#ifndef DPAC_PGX_DEPTH
-#define DPAC_PGX_DEPTH 1  // register stages of loads in flight (2 measured: no gain, 0.628 vs 0.628 ms at 204 800 rows)
-#endif
-constexpr int kPgxDepth = DPAC_PGX_DEPTH;
-#ifndef DPAC_PGX_ROWDESC
-#define DPAC_PGX_ROWDESC 0  // timing knob: per-row buffer descriptors in the staging loads
-#endif
-static_assert(kPgxDepth == 1 || kPgxDepth == 2, "1 or 2 stages");
 constexpr float kPgxLo = 4096.f, kPgxLoInv = 1.f / 4096.f;
-#ifndef DPAC_PGW_EARLY
-#define DPAC_PGW_EARLY 1  // issue the next sub-chunk's loads before the column scaling (round 6)
-#endif
 
 // staged values of one sub-chunk (registers; loaded before the previous sub-chunk's MFMAs)
 template <int QA, int QB, bool L0>
@@ -122,8 +111,6 @@ __device__ __forceinline__ void pgx_body(const PgArgs<float>& a, const int l, co
   const int wi = wave / WJ, wj = wave % WJ;
   const int rb = tid / FL, fl = tid % FL;
   static_assert(FL % 64 == 0, "a wave's lanes share one row block");
-  const int rbu = __builtin_amdgcn_readfirstlane(rb);
-  (void)rbu;
   const int64_t r_begin = chunk * a.rows_per_chunk;
   const int64_t r_end = min(a.rows, r_begin + a.rows_per_chunk);
   const bool first = L0 && grp == 0;  // also sums BN_0 (L0: l == 0)
@@ -168,33 +155,6 @@ __device__ __forceinline__ void pgx_body(const PgArgs<float>& a, const int l, co
 #pragma unroll
     for (int jj = 0; jj < NTJ; ++jj) acc[ti][jj] = pgf4{0.f, 0.f, 0.f, 0.f};
 
-#if DPAC_PGX_ROWDESC
-  // loads of the 32 rows at r0: one descriptor per row (wave-uniform: a wave's lanes share
-  // rb), based at the row and sized to it (0 past the chunk's end, so those rows read 0 and
-  // add nothing); the lane offsets are the column offsets alone, so no per-row VGPR offsets
-  // are hoisted out of the row loop (208 -> 180 VGPRs for the wide layers)
-  auto issue = [&](int64_t r0, PgxStage<QA, QB, L0>& st) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int64_t row = r0 + 8 * rbu + i;
-      const bool in = row < r_end;
-      const auto rA = make_rsrc(srcA + row * ldA, in ? (uint32_t)K * 4u : 0u);
-      const auto rG = make_rsrc(gA + row * a.gtot, (in && L0) ? (uint32_t)K * 4u : 0u);
-      const auto rB = make_rsrc(gB + row * a.gtot, in ? (uint32_t)(H - col0) * 4u : 0u);
-      const auto rZ = make_rsrc(zB + row * a.ztot, in ? (uint32_t)(H - col0) * 4u : 0u);
-#pragma unroll
-      for (int q = 0; q < QA; ++q) {
-        st.a[q][i] = buf_load_elem<float>(rA, offA[q]);
-        if constexpr (L0) st.g0[q][i] = first ? buf_load_elem<float>(rG, offG0[q]) : 0.f;
-      }
-#pragma unroll
-      for (int q = 0; q < QB; ++q) {
-        st.gb[q][i] = buf_load_elem<float>(rB, offB[q]);
-        st.zb[q][i] = buf_load_elem<float>(rZ, offB[q]);
-      }
-    }
-  };
-#else
   // loads of the 32 rows at r0: descriptors based at row r0 ending at the chunk's last row
   // (rows past it read 0, so their G is 0 and they add nothing); masked columns carry kOOB
   auto issue = [&](int64_t r0, PgxStage<QA, QB, L0>& st) {
@@ -218,11 +178,10 @@ __device__ __forceinline__ void pgx_body(const PgArgs<float>& a, const int l, co
       }
     }
   };
-#endif
 
   const int fq = lane >> 4, fi = lane & 15;  // fragment: row block, feature / column in the tile
   // one sub-chunk of 32 rows from its staged registers `st`, which are then refilled with
-  // the sub-chunk kPgxDepth ahead (kPgxDepth register stages in flight)
+  // the next sub-chunk (one register stage in flight; two measured no gain)
   auto sub = [&](int64_t r0, PgxStage<QA, QB, L0>& st) {
     __syncthreads();  // the previous sub-chunk's fragment reads are done
 #pragma unroll
@@ -263,8 +222,8 @@ __device__ __forceinline__ void pgx_body(const PgArgs<float>& a, const int l, co
       s_cmax[rb * CW + c] = m;
     }
     // round 6: the register stage is consumed (A into the image, B into vb and the sums), so the
-    // sub-chunk kPgxDepth ahead is issued now, under the column scaling as well as the MFMAs
-    if (DPAC_PGW_EARLY && r0 + kPgxDepth * kPgxSR < r_end) issue(r0 + kPgxDepth * kPgxSR, st);
+    // next sub-chunk is issued now, under the column scaling as well as the MFMAs
+    if (r0 + kPgxSR < r_end) issue(r0 + kPgxSR, st);
     __syncthreads();  // the column maxima of the sub-chunk
 #pragma unroll
     for (int q = 0; q < QB; ++q) {
@@ -295,7 +254,6 @@ __device__ __forceinline__ void pgx_body(const PgArgs<float>& a, const int l, co
       cexp[q] = e;
     }
     __syncthreads();
-    if (!DPAC_PGW_EARLY && r0 + kPgxDepth * kPgxSR < r_end) issue(r0 + kPgxDepth * kPgxSR, st);  // lands kPgxDepth sub-chunks later
     pgh8 bh[NTJ], bl[NTJ], b12[NTJ];
 #pragma unroll
     for (int jj = 0; jj < NTJ; ++jj) {
@@ -334,16 +292,7 @@ __device__ __forceinline__ void pgx_body(const PgArgs<float>& a, const int l, co
   };
   PgxStage<QA, QB, L0> st0;
   issue(r_begin, st0);
-  if constexpr (kPgxDepth == 1) {
-    for (int64_t r0 = r_begin; r0 < r_end; r0 += kPgxSR) sub(r0, st0);
-  } else {
-    PgxStage<QA, QB, L0> st1;
-    if (r_begin + kPgxSR < r_end) issue(r_begin + kPgxSR, st1);
-    for (int64_t r0 = r_begin; r0 < r_end; r0 += 2 * kPgxSR) {
-      sub(r0, st0);
-      if (r0 + kPgxSR < r_end) sub(r0 + kPgxSR, st1);
-    }
-  }
+  for (int64_t r0 = r_begin; r0 < r_end; r0 += kPgxSR) sub(r0, st0);
 
   // ---- this chunk's partial dW_l: lane holds features 4 fq .. +3 of its row tile, column fi ----
   float* part = a.part + chunk * a.ptot;
@@ -406,7 +355,6 @@ __device__ __forceinline__ void pgx_body(const PgArgs<float>& a, const int l, co
   }
   if (bad) x3_flag(a.status);
 }
-
 
 // ---------------------------------------------------------------------------------------------
 // k_param_grads_x3w: the wide hidden layers (K in (32, 208], H in (32, 256], l >= 1) and the
@@ -538,30 +486,18 @@ __device__ __forceinline__ void pgw_row_dma(const float* src, uint32_t voff, uns
                : "=&s"(keep) : "v"(voff), "s"(m0), "s"(base) : "memory");
 }
 
-// The same copy of a row of at most 128 bytes into a compact 128-byte slot: only the lanes
-// inside the row (and lane 0) issue, so nothing lands past dst + 128.
-__device__ __forceinline__ void pgw_row_dma_128(const float* src, uint32_t bytes, int lane, unsigned char* dst) {
-  if ((uint32_t)lane * 16u < bytes || lane == 0) pgw_row_dma(src, (uint32_t)lane * 16u, dst);
-}
-constexpr int kPgwRawG0c = kPgxSR * 128;  // merged launches: G_0 rows in compact 128-byte slots (K <= 32)
-
 // lsel >= 0: layer lsel, chunk blockIdx.x.  lsel < 0 (round 5, L0 = false): -lsel = l0 + 8 nl,
 // layers l0 .. l0 + nl - 1 in ONE launch, XCD-aware: each group of 8 nl workgroups holds 8 chunks
 // x the nl layers, and a chunk's workgroups are 8 apart (the dispatcher deals workgroups
 // round-robin over the 8 XCDs, so they share an XCD and run together): z_{l+1}, layer l's BN
 // operand and layer l+1's A, is read by both at about the same time and the second read can hit
-// L2 / the Infinity Cache.  A merged launch may start at the input layer (l0 = 0, K <= 32): its
-// workgroups run the L0 variant's arithmetic at run time (BN_0 only, BN_0's sums from G_0 rows,
-// which land in compact slots after the plan's LDS: the launch adds kPgwRawG0c bytes), bitwise
-// k_param_grads_x3w<NTI, true>'s results.
-// MODE 0: one layer (lsel >= 0); 1: a merged launch of wide / output layers; 2: a merged launch
-// that starts at the input layer (run-time L0 workgroups).  Separate instantiations: the run-time
-// L0 state costs registers the one-layer kernel does not have to spare (128 VGPRs at 1 024
-// threads; round 5 measured a 54-VGPR spill when every launch carried it).
+// L2 / the Infinity Cache.
+// MODE 0: one layer (lsel >= 0); 1: a merged launch of wide layers (the input layer keeps its own
+// L0 launch).
 template <int NTI, bool L0 = false, int MODE = 0>
 __global__ __launch_bounds__(kPgwThreads) void k_param_grads_x3w(const PgArgs<float> a, const int lsel) {
   using PL = PgwPlan<NTI, L0>;
-  static_assert(MODE == 0 || !L0, "merged launches use the run-time input layer");
+  static_assert(MODE == 0 || (MODE == 1 && !L0), "merged launches hold wide layers only");
   constexpr int KP = PL::KP, CW = kPgwCW;
   static_assert(KP <= 256, "one staging thread per feature");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // PL::kSmem bytes (dynamic)
@@ -587,12 +523,9 @@ __global__ __launch_bounds__(kPgwThreads) void k_param_grads_x3w(const PgArgs<fl
   const int64_t r_begin = chunk * a.rows_per_chunk;
   const int64_t r_end = min(a.rows, r_begin + a.rows_per_chunk);
   const bool last = l == a.L;
-  const bool rt0 = MODE == 2 && l == 0;   // the input layer inside a merged launch (see above)
-  const bool in0 = L0 || rt0;
-  const float* srcA = in0 ? a.x : a.z + a.zoff[l];  // L0: the network input (l = 0)
-  const int64_t ldA = in0 ? a.ldx : a.ztot;
-  const float* const rawG0 = reinterpret_cast<const float*>(smem + (L0 ? PL::kRawG0 : PL::kSmem));
-  const int g0ld = L0 ? CW : 32;  // floats per G_0 slot
+  const float* srcA = L0 ? a.x : a.z + a.zoff[l];  // L0: the network input (l = 0)
+  const int64_t ldA = L0 ? a.ldx : a.ztot;
+  const float* const rawG0 = reinterpret_cast<const float*>(smem + PL::kRawG0);
   const float* gB = a.G + a.goff[l + 1];
   const float* zB = a.z + a.zoff[l + 1];
   const int64_t ld = a.ztot;
@@ -619,7 +552,6 @@ __global__ __launch_bounds__(kPgwThreads) void k_param_grads_x3w(const PgArgs<fl
       pgw_row_dma(srcA + row * ldA, voffA, smem + PL::kRawA + i * CW * 4);
       pgw_row_dma(zB + row * ld, voffZ, smem + PL::kRawZ + i * CW * 4);
       if constexpr (L0) pgw_row_dma(a.G + a.goff[0] + row * a.gtot, voffA, smem + PL::kRawG0 + i * CW * 4);
-      else if (rt0) pgw_row_dma_128(a.G + a.goff[0] + row * a.gtot, (uint32_t)K * 4u, lane, smem + PL::kSmem + i * 128);
     }
   };
   auto issue_g = [&](int64_t r0) {
@@ -650,10 +582,10 @@ __global__ __launch_bounds__(kPgwThreads) void k_param_grads_x3w(const PgArgs<fl
         for (int i = 0; i < 8; ++i) {
           const float xv = rawA[(8 * rb + i) * CW + fl];
           const float y = ha + xv * sa;
-          if (in0) {  // BN_0 only (solver.py:260-262); its sums over the chunk's rows
+          if (L0) {  // BN_0 only (solver.py:260-262); its sums over the chunk's rows
             v[i] = fa ? y : 0.f;
             if (fa && r0 + 8 * rb + i < r_end) {
-              const float g0 = rawG0[(8 * rb + i) * g0ld + fl];
+              const float g0 = rawG0[(8 * rb + i) * CW + fl];
               cs0_b += g0;
               cs0_s += g0 * xv;
             }
@@ -684,9 +616,8 @@ __global__ __launch_bounds__(kPgwThreads) void k_param_grads_x3w(const PgArgs<fl
     __syncthreads();  // the column maxima; every raw row read
     // round 6: the next sub-chunk's raw rows (LDS-DMA: no registers) are issued here, as soon as
     // every raw row is read, so they land during the column scaling and split as well as the
-    // MFMAs; its G rows (a register stage) after the split as before (DPAC_PGW_EARLY=0: all after
-    // the split, rounds 4-5)
-    if (DPAC_PGW_EARLY && r0 + kPgxSR < r_end) issue_dma(r0 + kPgxSR);
+    // MFMAs; its G rows (a register stage) after the split as before
+    if (r0 + kPgxSR < r_end) issue_dma(r0 + kPgxSR);
     {
       const float m = fmaxf(fmaxf(s_cmax[fl], s_cmax[CW + fl]), fmaxf(s_cmax[2 * CW + fl], s_cmax[3 * CW + fl]));
       int e = cexp;
@@ -714,10 +645,7 @@ __global__ __launch_bounds__(kPgwThreads) void k_param_grads_x3w(const PgArgs<fl
     }
     // the next sub-chunk's rows (the raw rows are read; vb no longer needs gst): they land
     // during this sub-chunk's MFMAs
-    if (r0 + kPgxSR < r_end) {
-      if (DPAC_PGW_EARLY) issue_g(r0 + kPgxSR);  // the G register stage: live only from here
-      else issue(r0 + kPgxSR);
-    }
+    if (r0 + kPgxSR < r_end) issue_g(r0 + kPgxSR);  // the G register stage: live only from here
     __syncthreads();  // the images
     {
       const pgh8 bh = *reinterpret_cast<const pgh8*>(bBase);
@@ -758,296 +686,6 @@ __global__ __launch_bounds__(kPgwThreads) void k_param_grads_x3w(const PgArgs<fl
   float* red = reinterpret_cast<float*>(smem);
   red[(rb * 2 + 0) * CW + fl] = csb_b;
   red[(rb * 2 + 1) * CW + fl] = csb_s;
-  float* red0 = red + 4 * 2 * CW;  // L0: [4 rb][2][KP]
-  if (in0 && fl < KP) {
-    red0[(rb * 2 + 0) * KP + fl] = cs0_b;
-    red0[(rb * 2 + 1) * KP + fl] = cs0_s;
-  }
-  __syncthreads();
-  if (in0 && tid < K) {
-    float sb = 0.f, ss = 0.f;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      sb += red0[(w * 2 + 0) * KP + tid];
-      ss += red0[(w * 2 + 1) * KP + tid];
-    }
-    part[a.off_beta[0] + tid] = sb;
-    part[a.off_gamma[0] + tid] = ss;
-  }
-  if (tid < CW && tid < H) {
-    float sb = 0.f, ss = 0.f;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      sb += red[(w * 2 + 0) * CW + tid];
-      ss += red[(w * 2 + 1) * CW + tid];
-    }
-    part[a.off_beta[l + 1] + tid] = sb;
-    part[a.off_gamma[l + 1] + tid] = ss;
-  }
-  if (bad) x3_flag(a.status);
-}
-
-// ---------------------------------------------------------------------------------------------
-// k_param_grads_x3d (round 6): k_param_grads_x3w's sums, with the next
-// sub-chunk's loads in flight during this one's staging as well as its MFMAs.  x3w's 1 024-thread
-// workgroup has 128 VGPRs per lane and no LDS for a second raw block, so it issues the next loads
-// only after staging (measured: 3.7 TB/s of operand rows against 5.4 TB/s for the same row slices in
-// a plain streaming kernel, profiles/r05_call22_slice_bw.txt).  Here:
-//  * 8 wavefronts (512 threads, 256 VGPRs per lane), wave w owning the column tiles w and w + 8
-//    (NTI x 2 accumulator tiles), so each wave reads every A fragment for two column tiles and the
-//    A-image reads per sub-chunk halve;
-//  * G_{l+1} through registers and A's raw rows by LDS-DMA into two raw blocks: two stages (an
-//    unrolled pair of sub-chunks), each stage's loads issued as soon as its previous contents are
-//    consumed, so they are in flight through a whole sub-chunk; z_{l+1} (only the BN sums read it)
-//    by LDS-DMA into one raw block, issued once it is read (as x3w's), two phases ahead of use; the
-//    2^12 hi B operand is formed in registers (no third B image): 160 KiB of LDS at 13 tiles.
-// Arithmetic, order of every sum and partial layout are x3w's: bitwise its results.
-constexpr int kPgdThreads = 512;
-template <int NTI, bool L0 = false>
-struct PgdPlan {
-  static constexpr int KP = 16 * NTI;
-  static constexpr int kImgA = 2 * 4 * KP * 8 * 2;          // A hi, lo halves
-  static constexpr int kImgB = 2 * 4 * kPgwCW * 8 * 2;      // B hi, lo halves
-  static constexpr int kRaw = kPgxSR * kPgwCW * 4;          // one raw A block [32][256] floats
-  static constexpr int kRawA = kImgA + kImgB;               // two raw A blocks
-  static constexpr int kRawZ = kRawA + 2 * kRaw;            // one raw z_{l+1} block
-  static constexpr int kRawG0 = kRawZ + kRaw;               // L0: two compact G_0 blocks [32][32]
-  static constexpr int kCol = kRawG0 + (L0 ? 2 * kPgwRawG0c : 0);
-  static constexpr int kSmem = kCol + (4 * kPgwCW + 2 * kPgwCW) * 4;
-  static_assert(4 * 2 * kPgwCW * 4 + 4 * 2 * KP * 4 <= kRawA, "BN sums' reduction fits the image bytes");
-  static_assert(kSmem <= 160 * 1024, "LDS");
-};
-
-template <int NTI, bool L0 = false, int MODE = 0>
-__global__ __launch_bounds__(kPgdThreads) void k_param_grads_x3d(const PgArgs<float> a, const int lsel) {
-  using PL = PgdPlan<NTI, L0>;
-  constexpr int KP = PL::KP, CW = kPgwCW;
-  static_assert(MODE == 0 || !L0, "merged launches hold wide layers only");
-  static_assert(!L0 || KP <= 32, "the input layer: K <= 32");
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];  // PL::kSmem bytes (dynamic)
-  _Float16* const sA = reinterpret_cast<_Float16*>(smem);
-  _Float16* const sB = reinterpret_cast<_Float16*>(smem + PL::kImgA);
-  float* const s_cmax = reinterpret_cast<float*>(smem + PL::kCol);
-  float* const s_cfac = s_cmax + 4 * CW;
-  int* const s_cexp = reinterpret_cast<int*>(s_cfac + CW);
-  if (x3_status_set(a.status)) return;  // fell back: the f32 kernel after this one does the work
-  const int64_t bx = blockIdx.x;
-  const int nl = MODE == 0 ? 1 : (-lsel) >> 3;
-  const int l = MODE == 0 ? lsel : ((-lsel) & 7) + (int)((bx >> 3) % nl);
-  const int64_t chunk = MODE == 0 ? bx : (bx / (8 * nl)) * 8 + (bx & 7);
-  if (chunk * a.rows_per_chunk >= a.rows) return;  // past the last chunk (merged grid), before any barrier
-  bool bad = false;
-  const int K = a.width[l], H = a.width[l + 1];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // column tiles wave, wave + 8
-  const int rb = tid >> 7, fl = tid & 127;                     // staging: 8-row block; features / columns fl, fl + 128
-  const int rbu = __builtin_amdgcn_readfirstlane(rb);
-  const int64_t r_begin = chunk * a.rows_per_chunk;
-  const int64_t r_end = min(a.rows, r_begin + a.rows_per_chunk);
-  const bool last = l == a.L;
-  const float* srcA = L0 ? a.x : a.z + a.zoff[l];
-  const int64_t ldA = L0 ? a.ldx : a.ztot;
-  const float* gB = a.G + a.goff[l + 1];
-  const float* zB = a.z + a.zoff[l + 1];
-  float sa[2], ha[2], sbv[2], bbv[2], csb_b[2], csb_s[2];
-  uint32_t offB[2];
-  bool fa[2];
-  int cexp[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int k = fl + 128 * h;
-    fa[h] = k < K;
-    sa[h] = fa[h] ? a.scale[l][k] : 0.f;
-    ha[h] = fa[h] ? a.shift[l][k] : 0.f;
-    const bool fb = k < H;
-    sbv[h] = fb ? a.scale[l + 1][k] : 0.f;
-    bbv[h] = (fb && last) ? a.bias[k] : 0.f;
-    offB[h] = fb ? (uint32_t)k * 4u : kOOB;
-    csb_b[h] = csb_s[h] = 0.f;
-    cexp[h] = -100;
-  }
-  float cs0_b = 0.f, cs0_s = 0.f;  // L0: BN_0's sums, feature fl
-  pgf4 acc[NTI][2];  // 2^12 x (the column-scaled) dW tiles: features 16 t + 4 fq .., columns 16 (wave + 8 j) + fi
-#pragma unroll
-  for (int t = 0; t < NTI; ++t) acc[t][0] = acc[t][1] = pgf4{0.f, 0.f, 0.f, 0.f};
-  float gst[2][2][8];  // [stage][h][row]: G_{l+1} at rows 8 rb + i, columns fl + 128 h
-  const uint32_t voffA = pgw_lane_off((uint32_t)K * 4u, lane), voffZ = pgw_lane_off((uint32_t)H * 4u, lane);
-  const float* const rawZ = reinterpret_cast<const float*>(smem + PL::kRawZ);
-
-  // z_{l+1}'s 32 rows at r0 into the raw z block, wave w copying rows 4 w .. 4 w + 3 (past the
-  // chunk: its last row again; times G = 0 it adds nothing)
-  auto issue_z = [&](int64_t r0) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int i = 4 * wave + j;
-      pgw_row_dma(zB + min(r0 + i, r_end - 1) * a.ztot, voffZ, smem + PL::kRawZ + i * CW * 4);
-    }
-  };
-  // the 32 rows at r0 into stage S: G rows through registers, then the raw A rows (and G_0 rows)
-  // by LDS-DMA, wave w copying rows 4 w .. 4 w + 3.  Rows past the chunk: G reads 0, the DMA
-  // repeats the chunk's last row.
-  auto issue = [&](int64_t r0, auto sidx) {
-    constexpr int S = decltype(sidx)::value;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int64_t row = r0 + 8 * rbu + i;
-      const auto rB = make_rsrc(gB + row * a.gtot, row < r_end ? (uint32_t)H * 4u : 0u);
-#pragma unroll
-      for (int h = 0; h < 2; ++h) gst[S][h][i] = buf_load_elem<float>(rB, offB[h]);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int i = 4 * wave + j;
-      const int64_t row = min(r0 + i, r_end - 1);
-      pgw_row_dma(srcA + row * ldA, voffA, smem + PL::kRawA + S * PL::kRaw + i * CW * 4);
-      if constexpr (L0)
-        pgw_row_dma_128(a.G + a.goff[0] + row * a.gtot, (uint32_t)K * 4u, lane,
-                        smem + PL::kRawG0 + S * kPgwRawG0c + i * 128);
-    }
-  };
-  constexpr int kIssueOps = 16 + 4 * (L0 ? 2 : 1);  // vector memory instructions per wave and issue
-
-  const int fq = lane >> 4, fi = lane & 15;
-  const _Float16* const aBase = sA + (fq * KP + fi) * 8;  // + (part 4 KP + 16 t) 8
-  auto sub = [&](int64_t r0, auto sidx) {
-    constexpr int S = decltype(sidx)::value;
-    const float* const rawA = reinterpret_cast<const float*>(smem + PL::kRawA + S * PL::kRaw);
-    const float* const rawG0 = reinterpret_cast<const float*>(smem + PL::kRawG0 + S * kPgwRawG0c);
-    // this sub-chunk's rows have landed once only the issue made right after its z rows is
-    // outstanding: issues come in the order (G, A)_k .. z_k, (G, A)_{k+1}, so that is the next
-    // sub-chunk's (if any)
-    if (r0 + kPgxSR < r_end) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kIssueOps) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();  // raw rows in LDS; the previous sub-chunk's fragment reads are done
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {  // A: features fl + 128 h of rows 8 rb .. + 7, BN and the activation, split
-      const int k = fl + 128 * h;
-      if (h == 1 && 128 >= KP) continue;  // compile-time: no second feature
-      if (k < KP) {
-        float v[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const float xv = rawA[(8 * rb + i) * CW + k];
-          const float y = ha[h] + xv * sa[h];
-          if constexpr (L0) {  // BN_0 only (solver.py:260-262); its sums over the chunk's rows
-            v[i] = fa[h] ? y : 0.f;
-            if (fa[h] && r0 + 8 * rb + i < r_end) {
-              const float g0 = rawG0[(8 * rb + i) * 32 + k];
-              cs0_b += g0;
-              cs0_s += g0 * xv;
-            }
-          } else {
-            v[i] = fa[h] ? y + fmaxf(y, 0.f) : 0.f;  // hidden activations
-          }
-        }
-        pgh8 hh, lo;
-        pgx_split8(v, hh, lo);
-        bad |= x3_bad4(v[0], v[1], v[2], v[3]) | x3_bad4(v[4], v[5], v[6], v[7]);
-        *reinterpret_cast<pgh8*>(sA + ((0 * 4 + rb) * KP + k) * 8) = hh;
-        *reinterpret_cast<pgh8*>(sA + ((1 * 4 + rb) * KP + k) * 8) = lo;
-      }
-    }
-    float vb[2][8];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {  // B: columns fl + 128 h, their sums and the sub-chunk's column max
-      float m = 0.f;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const float gv = gst[S][h][i];
-        vb[h][i] = gv * sbv[h];
-        m = fmaxf(m, fabsf(vb[h][i]));
-        csb_b[h] += gv;
-        csb_s[h] += gv * (rawZ[(8 * rb + i) * CW + fl + 128 * h] + bbv[h]);  // bbv = 0 unless the output layer
-      }
-      s_cmax[rb * CW + fl + 128 * h] = m;
-    }
-    __syncthreads();  // the column maxima; every raw row of this stage read
-    if (r0 + kPgxSR < r_end) issue_z(r0 + kPgxSR);              // the raw z block is free: the next sub-chunk's
-    if (r0 + 2 * kPgxSR < r_end) issue(r0 + 2 * kPgxSR, sidx);  // this stage is free: two sub-chunks ahead
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int c = fl + 128 * h;
-      const float m = fmaxf(fmaxf(s_cmax[c], s_cmax[CW + c]), fmaxf(s_cmax[2 * CW + c], s_cmax[3 * CW + c]));
-      int e = cexp[h];
-      if (m > 0.f && m < 3.0e38f) {
-        int em = 0;
-        (void)frexpf(m, &em);
-        e = em > cexp[h] ? em : cexp[h];
-      }
-      const float sc = ldexpf(1.f, 3 - e);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) vb[h][i] *= sc;
-      pgh8 hh, lo;
-      pgx_split8(vb[h], hh, lo);
-      bad |= x3_bad4(vb[h][0], vb[h][1], vb[h][2], vb[h][3]) | x3_bad4(vb[h][4], vb[h][5], vb[h][6], vb[h][7]);
-      *reinterpret_cast<pgh8*>(sB + ((0 * 4 + rb) * CW + c) * 8) = hh;
-      *reinterpret_cast<pgh8*>(sB + ((1 * 4 + rb) * CW + c) * 8) = lo;
-      if (rb == 0) {
-        s_cfac[c] = ldexpf(1.f, cexp[h] - e);
-        s_cexp[c] = e;
-      }
-      cexp[h] = e;
-    }
-    __syncthreads();  // the images
-    pgh8 bh[2], bl[2], b12[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int cT = (wave + 8 * j) * 16 + fi;
-      bh[j] = *reinterpret_cast<const pgh8*>(sB + (fq * CW + cT) * 8);
-      bl[j] = *reinterpret_cast<const pgh8*>(sB + ((4 + fq) * CW + cT) * 8);
-      b12[j] = bh[j] * (_Float16)kPgxLo;  // exact: |hi| < 8
-      const float f = s_cfac[cT];
-      if (__any(f != 1.f)) {
-#pragma unroll
-        for (int t = 0; t < NTI; ++t) acc[t][j] *= f;
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < NTI; ++t) {
-      const pgh8 xh = *reinterpret_cast<const pgh8*>(aBase + 16 * t * 8);
-      const pgh8 xl = *reinterpret_cast<const pgh8*>(aBase + (4 * KP + 16 * t) * 8);
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, b12[j], acc[t][j], 0, 0, 0);
-        acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, bl[j], acc[t][j], 0, 0, 0);
-        acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xl, bh[j], acc[t][j], 0, 0, 0);
-      }
-    }
-  };
-  using S0 = std::integral_constant<int, 0>;
-  using S1 = std::integral_constant<int, 1>;
-  issue(r_begin, S0{});
-  issue_z(r_begin);
-  if (r_begin + kPgxSR < r_end) issue(r_begin + kPgxSR, S1{});
-  for (int64_t r0 = r_begin; r0 < r_end; r0 += 2 * kPgxSR) {
-    sub(r0, S0{});
-    if (r0 + kPgxSR < r_end) sub(r0 + kPgxSR, S1{});
-  }
-
-  // ---- this chunk's partial dW_l: lane holds features 16 t + 4 fq .. +3, columns cT_j ----
-  float* part = a.part + chunk * a.ptot;
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int cT = (wave + 8 * j) * 16 + fi;
-    const float us = ldexpf(1.f, s_cexp[cT] - 3 - 12);  // undo 2^12 and the column scale
-#pragma unroll
-    for (int t = 0; t < NTI; ++t) {
-      const pgf4 c = acc[t][j] * us;
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        const int k = 16 * t + 4 * fq + v;
-        if (k < K && cT < H) part[a.off_W[l] + (int64_t)k * H + cT] = c[v];
-      }
-    }
-  }
-  // ---- BN column sums: combine the 4 row blocks through LDS (reusing the images) ----
-  __syncthreads();
-  float* red = reinterpret_cast<float*>(smem);
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    red[(rb * 2 + 0) * CW + fl + 128 * h] = csb_b[h];
-    red[(rb * 2 + 1) * CW + fl + 128 * h] = csb_s[h];
-  }
   float* red0 = red + 4 * 2 * CW;  // L0: [4 rb][2][KP]
   if (L0 && fl < KP) {
     red0[(rb * 2 + 0) * KP + fl] = cs0_b;

@@ -19,26 +19,16 @@ namespace dpac {
 
 constexpr int kMrThreads = 256;
 constexpr int kMrWaves = 4;
-#ifndef DPAC_MR_LD_PAD
-#define DPAC_MR_LD_PAD 8  // row stride 264 = 8 mod 64 dwords: conflict-free ds_read_b128 A reads on gfx950 (+4 left 2-way conflicts)
-#endif
-constexpr int kMrLd = DPAC_MLP_MAX_WIDTH + DPAC_MR_LD_PAD;  // LDS row stride: 16 rows x 4 k hit 64 banks
+// LDS row stride 264 = 8 mod 64 dwords: 16 rows x 4 k hit 64 banks, conflict-free ds_read_b128 A
+// reads on gfx950 (a pad of 4 left 2-way conflicts)
+constexpr int kMrLd = DPAC_MLP_MAX_WIDTH + 8;
 constexpr int kMrPrefetch = 8;
-#ifndef DPAC_MR_ROT
-#define DPAC_MR_ROT 0  // rotate the waves' column-tile sets per workgroup (timing knob)
-#endif
-#ifndef DPAC_MR_PIN
-#define DPAC_MR_PIN 0  // sched_barrier after each k group of the k-major layers (timing knob)
-#endif
 
 template <typename T>
 struct MrCfg;
-#ifndef DPAC_MR_RT_F32
-#define DPAC_MR_RT_F32 1
-#endif
 template <>
 struct MrCfg<float> {
-  static constexpr int RT = DPAC_MR_RT_F32;  // 16 rows per workgroup: occupancy beats B reuse (measured)
+  static constexpr int RT = 1;  // 16 rows per workgroup: occupancy beats B reuse (measured)
 };
 template <>
 struct MrCfg<double> {
@@ -300,9 +290,6 @@ __device__ __forceinline__ void mr_layer_nt_km(const float* in, int K, int Nout,
           for (int rt = 0; rt < RT; ++rt) acc[rt][j] = MF::mma(av[q][rt][e], bq[q][j][e], acc[rt][j]);
         bq[q][j] = loadB(s0 + q + PG, j);
       }
-#if DPAC_MR_PIN
-      __builtin_amdgcn_sched_barrier(0);  // keep the B ring PG groups ahead (dpac_rollout_nn.h)
-#endif
     }
 #pragma unroll
     for (int q = 0; q < PG; ++q)
@@ -434,16 +421,8 @@ struct MrBwdEpi {
   }
 };
 
-// The wave's column-tile set.  13 tiles over 4 waves leave one wave with 4; with
-// DPAC_MR_ROT the heavy set rotates over the workgroups that share a CU (the
-// dispatcher deals blocks round-robin over the 8 XCDs, so blocks b, b+8, ... share
-// an XCD).  Each tile is still computed by one wave in one k order: bitwise the same.
-__device__ __forceinline__ int mr_wave(int tid) {
-  int w = tid / 64;
-  if constexpr (DPAC_MR_ROT == 1) w = (w + (int)(blockIdx.x >> 3)) & (kMrWaves - 1);
-  if constexpr (DPAC_MR_ROT == 2) w = (w + (int)blockIdx.x) & (kMrWaves - 1);
-  return __builtin_amdgcn_readfirstlane(w);
-}
+// The wave's column-tile set (wave, wave + 4, ...).  13 tiles over 4 waves leave one wave with 4.
+__device__ __forceinline__ int mr_wave(int tid) { return __builtin_amdgcn_readfirstlane(tid / 64); }
 
 template <typename T>
 __global__ __launch_bounds__(kMrThreads) void k_mlp_rows_fwd(const MrArgs<T> a) {

@@ -47,21 +47,12 @@ typedef float x3f4 __attribute__((ext_vector_type(4)));
 
 constexpr int kX3Waves = 8;
 constexpr int kX3Threads = 64 * kX3Waves;
-#ifndef DPAC_X3_RT
-#define DPAC_X3_RT 4  // row tiles per workgroup of the forward (timing knob)
-#endif
-#ifndef DPAC_X3_RT_BWD
-#define DPAC_X3_RT_BWD 2  // of the backward chain: at 4 it needs > 256 VGPRs and spills 432 B per lane
-#endif
-constexpr int kX3RT = DPAC_X3_RT;         // row tiles per workgroup (forward)
+constexpr int kX3RT = 4;                  // row tiles per workgroup (forward)
 constexpr int kX3Rows = 16 * kX3RT;       // 64 rows
-constexpr int kX3RTB = DPAC_X3_RT_BWD;    // row tiles per workgroup (backward)
+constexpr int kX3RTB = 2;                 // of the backward chain: at 4 it needs > 256 VGPRs, spills 432 B per lane
 constexpr int kX3RowsB = 16 * kX3RTB;     // 32 rows
 constexpr int kX3MaxChunks = (DPAC_MLP_MAX_WIDTH + 31) / 32;  // 8
-#ifndef DPAC_X3_LDPAD
-#define DPAC_X3_LDPAD 16  // halves of padding per LDS row (a multiple of 8: 16-byte rows)
-#endif
-constexpr int kX3Ld = 64 * kX3MaxChunks + DPAC_X3_LDPAD;      // halves per LDS row (1056 B at 16)
+constexpr int kX3Ld = 64 * kX3MaxChunks + 16;  // halves per LDS row: 16 of padding (1056 B, 16-byte rows)
 constexpr float kX3LoScale = 4096.f;      // 2^12
 constexpr float kX3LoInv = 1.f / 4096.f;
 constexpr int kX3MaxNT = (DPAC_MLP_MAX_WIDTH / 16 + kX3Waves - 1) / kX3Waves;  // 2
@@ -88,18 +79,7 @@ __device__ uint32_t g_x3_trace[256 * 8 * 16];  // [block][wave][point]
   } while (0)
 #endif
 
-#ifndef DPAC_X3_SPF
-#define DPAC_X3_SPF 2  // chunks of weights in flight ahead of the one being multiplied (forward)
-#endif
-#ifndef DPAC_X3_SPF_BWD
-#define DPAC_X3_SPF_BWD 2  // the same for the backward chain
-#endif
-#ifndef DPAC_X3_BWD_MINB
-#define DPAC_X3_BWD_MINB 1  // min waves per SIMD the backward is compiled for (launch bounds; timing knob)
-#endif
-#ifndef DPAC_X3_MASK_EARLY
-#define DPAC_X3_MASK_EARLY 1  // the backward's sign-bit word loaded before the K loop (1) or after it (0)
-#endif
+constexpr int kX3Spf = 2;  // chunks of weights in flight ahead of the one being multiplied (both chains)
 
 __device__ __forceinline__ void x3_split(float a, _Float16& hi, _Float16& lo) {
   hi = (_Float16)a;
@@ -271,7 +251,7 @@ __device__ __forceinline__ bool x3_layer_t(const _Float16* in, int K, int Nout, 
   return bad;
 }
 
-template <int RT = kX3RT, int SPF = DPAC_X3_SPF, class EPI>
+template <int RT = kX3RT, int SPF = kX3Spf, class EPI>
 __device__ __forceinline__ bool x3_layer(const _Float16* in, int K, int Nout, const _Float16* Wx3, int wave,
                                          int lane, EPI& epi) {
   const int ntiles = (Nout + 15) / 16;
@@ -328,6 +308,7 @@ struct X3Args {
   int64_t nblk;  // ceil(rows / 64)
 };
 constexpr int kX3MaskWords = 512;  // per hidden layer and 64-row block
+static_assert(kX3Rows == 64, "the forward's workgroup is the mask's 64-row block");
 static_assert(4 % kX3RTB == 0, "a backward workgroup's row tiles lie in one 64-row mask block");
 static_assert(kX3Waves == 8 && kX3MaxNT == 2, "the mask word holds 2 tiles x 4 row tiles of one lane");
 
@@ -424,7 +405,7 @@ struct X3BwdEpi {
   x3f4 s[kX3MaxNT], sh[kX3MaxNT];
   float ri[RT];
   x3f4 zz[MASKED ? 1 : kX3MaxNT][MASKED ? 1 : RT];  // z_l of the lane's quads, loaded in post()
-  uint32_t mword;              // MASKED: the lane's mask word (loaded in post())
+  uint32_t mword;              // MASKED: the lane's mask word (loaded in pre())
   template <int NT>
   __device__ __forceinline__ void pre(int wave, int lane) {
 #pragma unroll
@@ -439,13 +420,11 @@ struct X3BwdEpi {
     }
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) ri[rt] = rinv[rt * 16 + (lane & 15)];
-    if constexpr (!FIRST && MASKED && DPAC_X3_MASK_EARLY) mword = mp[lane] >> mshift;
+    if constexpr (!FIRST && MASKED) mword = mp[lane] >> mshift;  // the sign-bit word: before the K loop
   }
   template <int NT>
   __device__ __forceinline__ void post(int wave, int lane) {  // every z load, then one wait
-    if constexpr (!FIRST && MASKED) {
-      if constexpr (!DPAC_X3_MASK_EARLY) mword = mp[lane] >> mshift;
-    } else if constexpr (!FIRST) {
+    if constexpr (!FIRST && !MASKED) {
 #pragma unroll
       for (int j = 0; j < NT; ++j) {
         const int f0 = x3_f0(wave, j, lane), nv = x3_nvalid(f0, Nout);
@@ -587,7 +566,7 @@ __global__ __launch_bounds__(kX3Threads) void k_mlp_rows_fwd_x3(const X3Args a) 
 
 // MASKED: the activation factors from the forward's sign-bit bytes (a.mask) instead of z
 template <bool MASKED>
-__global__ __launch_bounds__(kX3Threads, DPAC_X3_BWD_MINB) void k_mlp_rows_bwd_x3(const X3Args a) {
+__global__ __launch_bounds__(kX3Threads, 1) void k_mlp_rows_bwd_x3(const X3Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char x3_lds[];
   _Float16* const img0 = reinterpret_cast<_Float16*>(x3_lds);
   _Float16* const img1 = reinterpret_cast<_Float16*>(x3_lds + kX3ImgBytesB);
@@ -680,12 +659,12 @@ __global__ __launch_bounds__(kX3Threads, DPAC_X3_BWD_MINB) void k_mlp_rows_bwd_x
                                   MASKED ? a.mask + ((int64_t)(l - 1) * a.nblk + (row0 >> 6)) * kX3MaskWords + wave * 64
                                          : nullptr,
                                   8 * (int)((row0 & 63) >> 4)};
-      bad |= x3_layer<kX3RTB, DPAC_X3_SPF_BWD>(img(pq), a.width[l + 1], a.width[l], a.wx3[l], wave, lane, epi);
+      bad |= x3_layer<kX3RTB, kX3Spf>(img(pq), a.width[l + 1], a.width[l], a.wx3[l], wave, lane, epi);
     } else {
       X3BwdEpi<true> epi{2 + 2 * L, nullptr, nullptr, rows_live, a.width[0], img(pq ^ 1), make_rsrc(nullptr, 0), 0, rg, a.gtot,
                          x3_rows_rsrc(a.g_x, row0, rows_live, a.width[0]), a.g_x != nullptr, a.scale[0], rinv,
                          nullptr, gp, a.g_x ? a.g_x + row0 * a.width[0] : nullptr, nullptr, 0};
-      x3_layer<kX3RTB, DPAC_X3_SPF_BWD>(img(pq), a.width[1], a.width[0], a.wx3[0], wave, lane, epi);  // dL/dx: not split again
+      x3_layer<kX3RTB, kX3Spf>(img(pq), a.width[1], a.width[0], a.wx3[0], wave, lane, epi);  // dL/dx: not split again
     }
     __syncthreads();
     X3_MARK(3 + 2 * (L - l));
