@@ -10,6 +10,6 @@ provides device memory, streams, HIP graphs and torch.distributed (RCCL).
 from . import _lib, config, equation, ops, parallel, solver  # noqa: F401
 from .config import load_config, munchify, set_floatx  # noqa: F401
 from .equation import EKN, LQR, LQR_var, VDP, Equation, TrajectoryBatch, ekn  # noqa: F401
-from .solver import ActorCriticSolver, ActorModel, CriticModel, DeepNN  # noqa: F401
+from .solver import ActorCriticSolver, ActorModel, CriticModel, DeepNN, PolicyEvaluation  # noqa: F401
 
 __version__ = "0.1.0"

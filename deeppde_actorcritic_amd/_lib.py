@@ -101,6 +101,8 @@ SIGNATURES = {
     "dpac_rollout_nn_mask_bytes": [_MLP, _I32, _I64, _I32],
     "dpac_rollout_nn_fwd": [_EQ, _I32, _I32, _I64, _I32, _D, _MLP, _P, _P, _P, _P, _P, _P, _I32, _P,
                             _P, _P, _P, _P, _P, _PI32, _P],
+    "dpac_policy_cost": [_EQ, _I32, _I32, _I64, _I32, _D, _MLP, _P, _P, _U64, _I64, _I32, _I32, _P, _P,
+                         _P, _P, _P, _P],
     "dpac_rollout_nn_bwd": [_EQ, _I32, _I32, _I64, _I32, _D, _MLP, _PP, _PP, _P, _P, _P, _P, _P, _P,
                             _P, _P, _P, _P, _P, _P, _P],
     "dpac_mlp_rows_mask_bytes": [_MLP, _I32, _I64],

@@ -206,8 +206,15 @@ OpArgs blank(const dpac_eqn_params* eq, int op, int32_t scheme, int32_t dtype, i
   return a;
 }
 
+// the dispatch-table call every launch ends in, after its size checks
+int dispatch(const OpArgs& a) {
+  const DispatchFn fn = find_dispatch(a.eq.eqn, a.eq.dim, a.dtype == DPAC_F64 ? 1 : 0);
+  const int r = fn ? fn(a) : DPAC_EUNSUP;
+  if (r == DPAC_EUNSUP) return fail(r, "no kernel for equation %d dim %d", a.eq.eqn, a.eq.dim);
+  return finish(r);
+}
+
 int launch(const OpArgs& a) {
-  int r = DPAC_EUNSUP;
   const bool f64 = a.dtype == DPAC_F64;
   // Kernels address each [N+1][B][d] / [N][B][c] / [B][N] array through one
   // 32-bit buffer descriptor whose offsets >= 2^31 mean "out of range".
@@ -222,10 +229,25 @@ int launch(const OpArgs& a) {
     return fail(DPAC_EINVAL, "batch too large for one launch: every [N+1][B][d] array must stay "
                 "below 2 GiB (B=%lld, N=%d, d=%d); split the batch over launches with "
                 "traj_offset", (long long)a.B, a.N, a.eq.dim);
-  const DispatchFn fn = find_dispatch(a.eq.eqn, a.eq.dim, f64 ? 1 : 0);
-  r = fn ? fn(a) : DPAC_EUNSUP;
-  if (r == DPAC_EUNSUP) return fail(r, "no kernel for equation %d dim %d", a.eq.eqn, a.eq.dim);
-  return finish(r);
+  return dispatch(a);
+}
+
+// dpac_policy_cost's launch: the lean kernels address no [N+1][B][d] array, and x0 / x_end only
+// through descriptors over a workgroup's own rows; the limit is the [B][d] array's byte count in
+// 32 bits.  dw, where it is given, is read through one descriptor like every [N][B][d] array.
+int launch_lean(const OpArgs& a) {
+  const int64_t esz = a.dtype == DPAC_F64 ? 8 : 4;
+  if (a.eq.dim > (1 << 16)) return fail(DPAC_EINVAL, "dim %d too large", a.eq.dim);
+  const int64_t row_bytes = a.B * a.eq.dim * esz;  // B <= 2^31, dim <= 2^16: no overflow
+  if (row_bytes >= (int64_t)1 << 32)
+    return fail(DPAC_EINVAL, "batch too large for one launch: a [B][d] array must stay below 4 GiB "
+                "(B=%lld, d=%d); split the batch over launches with traj_offset", (long long)a.B, a.eq.dim);
+  const int64_t limit = (int64_t)1 << 31;
+  if (a.dw && (row_bytes >= limit || (int64_t)a.N > (limit - 1) / row_bytes))
+    return fail(DPAC_EINVAL, "batch too large for one launch: the dw [N][B][d] array must stay below "
+                "2 GiB (B=%lld, N=%d, d=%d); pass dw = NULL to draw the increments in-kernel, or split "
+                "the batch over launches", (long long)a.B, a.N, a.eq.dim);
+  return dispatch(a);
 }
 
 // The equation's elementwise sigma as (sa, sb) and k_td's lane split, for the fused
@@ -364,6 +386,29 @@ int dpac_rollout_nn_fwd(const dpac_eqn_params* eq, int32_t scheme, int32_t dtype
   a.disc = disc; a.save_z = save_z; a.save_flag = save_flag; a.save_disc = save_disc;
   a.save_mask = save_mask; a.mask_written = mask_written;
   return launch(a);
+}
+
+int dpac_policy_cost(const dpac_eqn_params* eq, int32_t scheme, int32_t dtype, int64_t num_sample,
+                     int32_t num_steps, double total_time, const dpac_mlp* actor, const void* x0,
+                     const void* dw, uint64_t seed, int64_t traj_offset, int32_t sample_type,
+                     int32_t cost_order, void* y, void* disc, void* x_end, void* tau, int32_t* steps,
+                     void* stream) {
+  if (int e = check_run(eq, scheme, dtype, num_sample, num_steps, total_time)) return e;
+  if (int e = check_mlp(eq, actor)) return e;
+  DPAC_REQUIRE(x0);
+  DPAC_REQUIRE(y);
+  DPAC_REQUIRE(disc);
+  DPAC_REQUIRE(x_end);
+  if (int e = check_cost_order(cost_order)) return e;
+  if (!dw) {
+    if (int e = check_sample_type(sample_type)) return e;
+    if (traj_offset < 0) return fail(DPAC_EINVAL, "traj_offset must be >= 0");
+  }
+  OpArgs a = blank(eq, OP_ROLLOUT_NN, scheme, dtype, num_sample, num_steps, total_time, stream);
+  a.x0 = x0; a.dw = dw; a.mlp = *actor; a.seed = seed; a.traj_offset = traj_offset;
+  a.sample_type = dw_sample_type(sample_type);
+  a.cost_order = cost_order; a.y = y; a.disc = disc; a.x_end = x_end; a.tau = tau; a.steps = steps;
+  return launch_lean(a);
 }
 
 int dpac_rollout_nn_bwd(const dpac_eqn_params* eq, int32_t scheme, int32_t dtype,

@@ -473,21 +473,11 @@ __device__ __forceinline__ void draw_slot_pair(uint64_t seed, uint64_t traj, int
   for (int i = 0; i < 2 * M; ++i) out[i] = v[i];
 }
 
-// The M increments of lane slot p (components p*M + m) at step t.
+// The M increments of lane slot p at step t in the per-step layout (dw_steps_per_block == 1).
 template <typename T, int D>
-__device__ __forceinline__ void draw_slot(uint64_t seed, uint64_t traj, int t, int p,
-                                          int sample_type, T (&out)[comps_per_lane(D)]) {
+__device__ __forceinline__ void draw_slot_single(uint64_t seed, uint64_t traj, int t, int p,
+                                                 int sample_type, T (&out)[comps_per_lane(D)]) {
   constexpr int P = lanes_for_dim(D), M = comps_per_lane(D);
-  if constexpr (2 * M <= 4) {
-    if (dw_steps_per_block<T>(M, sample_type) == 2) {  // the paired layout: this step's half
-      T v[2 * M];
-      draw_slot_pair<T, D>(seed, traj, t >> 1, p, sample_type, v);
-      const bool odd = (t & 1) != 0;
-#pragma unroll
-      for (int m = 0; m < M; ++m) out[m] = odd ? v[M + m] : v[m];
-      return;
-    }
-  }
   if (sample_type == DPAC_SAMPLE_BOUNDED) {
     constexpr int PB = 4, BPL = (M + PB - 1) / PB;
     const uint64_t base = ((uint64_t)t * P + p) * BPL;
@@ -511,6 +501,24 @@ __device__ __forceinline__ void draw_slot(uint64_t seed, uint64_t traj, int t, i
         if (blk * PB + e < M) out[blk * PB + e] = n[e];
     }
   }
+}
+
+// The M increments of lane slot p (components p*M + m) at step t.
+template <typename T, int D>
+__device__ __forceinline__ void draw_slot(uint64_t seed, uint64_t traj, int t, int p,
+                                          int sample_type, T (&out)[comps_per_lane(D)]) {
+  constexpr int M = comps_per_lane(D);
+  if constexpr (2 * M <= 4) {
+    if (dw_steps_per_block<T>(M, sample_type) == 2) {  // the paired layout: this step's half
+      T v[2 * M];
+      draw_slot_pair<T, D>(seed, traj, t >> 1, p, sample_type, v);
+      const bool odd = (t & 1) != 0;
+#pragma unroll
+      for (int m = 0; m < M; ++m) out[m] = odd ? v[M + m] : v[m];
+      return;
+    }
+  }
+  draw_slot_single<T, D>(seed, traj, t, p, sample_type, out);
 }
 
 // All D increments of step t in component order (for one-lane-per-trajectory kernels).

@@ -70,6 +70,8 @@ struct OpArgs {
   uint8_t* save_mask;            // OP_ROLLOUT_NN: optional sign-bit mask (fast path only)
   int32_t* mask_written;         // OP_ROLLOUT_NN: host flag, 1 if the mask was written
   const uint8_t* mask_in;        // OP_ROLLOUT_NN_BWD: the forward's mask, or null
+  void *x_end, *tau;             // OP_ROLLOUT_NN: x_end selects the lean modes (dpac_policy_cost;
+  int32_t* steps;                //   dw null: in-kernel noise from seed / traj_offset / sample_type)
   const void* mlp_wt[DPAC_MLP_MAX_HIDDEN + 1];  // OP_ROLLOUT_NN_BWD: (W_i diag s_{i+1})^T
   hipStream_t stream;
 };

@@ -97,6 +97,12 @@ void with_out(int out, F&& f) {  // the rollout's optional outputs
   }
 }
 
+template <class F>
+void with_lean(int mode, F&& f) {  // the lean modes of the NN forward kernels (NnMode)
+  if (mode == kNnLeanPhilox) f(std::integral_constant<int, kNnLeanPhilox>{});
+  else f(std::integral_constant<int, kNnLeanDw>{});
+}
+
 // A launch with more dynamic LDS than the default limit.  Returns the attribute call's error
 // and does not launch after one.
 template <class K, class... A>
@@ -329,6 +335,11 @@ int launch_rollout_nn(const OpArgs& a, const E& eq, const DevConsts<T>& c, hipSt
   r.save_z = (T*)a.save_z; r.save_disc = (T*)a.save_disc; r.save_flag = a.save_flag;
   r.save_mask = nullptr;
   r.mb = nn_mask_tile_bytes(m.L);
+  // dpac_policy_cost: the lean instantiations of the kernel chosen below (always with the cost,
+  // never with saves or a mask), dw read (kNnLeanDw) or drawn in-kernel (kNnLeanPhilox)
+  const int mode = a.x_end ? (a.dw ? kNnLeanDw : kNnLeanPhilox) : kNnFull;
+  r.x_end = (T*)a.x_end; r.tau = (T*)a.tau; r.steps = a.steps;
+  r.seed = a.seed; r.traj_offset = a.traj_offset; r.sample_type = a.sample_type;
   const bool cost = a.y != nullptr;
   const int gphase = m.status ? a.mlp.guard_phase : DPAC_GUARD_INLINE;  // dpac.h guard_phase
   if constexpr (std::is_same<T, float>::value) {
@@ -341,9 +352,16 @@ int launch_rollout_nn(const OpArgs& a, const E& eq, const DevConsts<T>& c, hipSt
       const int rg = a.B <= 1024 ? 1 : 2;
       const dim3 g4((unsigned)((a.B + 4 * rg - 1) / (4 * rg))), b4(kN4Threads);
       with_scheme(a.scheme, [&](auto sch) {
-        with_bool(cost, [&](auto co) {
-          with_bool(rg == 2, [&](auto two) {
-            constexpr int RG = decltype(two)::value ? 2 : 1;
+        with_bool(rg == 2, [&](auto two) {
+          constexpr int RG = decltype(two)::value ? 2 : 1;
+          if (mode != kNnFull) {
+            with_lean(mode, [&](auto md) {
+              hipLaunchKernelGGL((k_rollout_nn4<T, E, D, decltype(sch)::value, true, RG, decltype(md)::value>), g4,
+                                 b4, 0, s, eq, c, m, r);
+            });
+            return;
+          }
+          with_bool(cost, [&](auto co) {
             hipLaunchKernelGGL((k_rollout_nn4<T, E, D, decltype(sch)::value, decltype(co)::value, RG>), g4, b4, 0,
                                s, eq, c, m, r);
           });
@@ -370,6 +388,13 @@ int launch_rollout_nn(const OpArgs& a, const E& eq, const DevConsts<T>& c, hipSt
       if (gphase != DPAC_GUARD_FALLBACK_ONLY) {
         hipError_t e = hipSuccess;
         with_scheme(a.scheme, [&](auto sch) {
+          if (mode != kNnFull) {
+            with_lean(mode, [&](auto md) {
+              e = launch_dyn_lds(k_rollout_nn_x3<E, D, decltype(sch)::value, true, false, false, decltype(md)::value>,
+                                 xgrid, nblock, NxLds::total, s, eq, c, m, r);
+            });
+            return;
+          }
           with_bool(cost, [&](auto co) {
             auto go = [&](auto sv, auto mk) {
               e = launch_dyn_lds(k_rollout_nn_x3<E, D, decltype(sch)::value, decltype(co)::value,
@@ -389,6 +414,18 @@ int launch_rollout_nn(const OpArgs& a, const E& eq, const DevConsts<T>& c, hipSt
   }
   if (gphase == DPAC_GUARD_FALLBACK_ONLY && !r.guard) return 0;  // phase 1 did the whole work
   with_scheme(a.scheme, [&](auto sch) {
+    if (mode != kNnFull) {
+      with_lean(mode, [&](auto md) {
+        constexpr int SCH = decltype(sch)::value, MD = decltype(md)::value;
+        if (m.fast)
+          hipLaunchKernelGGL((k_rollout_nn<T, E, D, SCH, true, 1, kNnFastOk<T>, false, MD>), ngrid, nblock, 0, s, eq,
+                             c, m, r);
+        else
+          hipLaunchKernelGGL((k_rollout_nn<T, E, D, SCH, true, 1, false, false, MD>), ngrid, nblock, 0, s, eq, c, m,
+                             r);
+      });
+      return;
+    }
     with_bool(cost, [&](auto co) {
       constexpr int SCH = decltype(sch)::value;
       constexpr bool CO = decltype(co)::value, FAST = kNnFastOk<T>;

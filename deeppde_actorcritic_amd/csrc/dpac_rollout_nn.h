@@ -76,7 +76,139 @@ struct NnRolloutArgs {
   const uint32_t* guard;  // the f32 fallback of a split-fp16 launch: run only once this word
                           // is set (dpac.h dpac_mlp.status); null = always run
   int tr;               // k_rollout_nn_x3: trajectories per workgroup (16, or 8: half a row tile)
+  // the lean modes (NnMode, dpac_policy_cost): per-path outputs and the Philox key
+  T *x_end, *tau;       // [B][d] the state after step N; [B] sum of coef*dt, or null
+  int32_t* steps;       // [B] sum of coef (steps taken before the path stopped), or null
+  uint64_t seed;
+  int64_t traj_offset;
+  int sample_type;
 };
+
+// Mode of the three NN forward kernels (k_rollout_nn, k_rollout_nn4, k_rollout_nn_x3), a template
+// constant so the time loop never tests it.  The lean modes serve dpac_policy_cost: x, dt, coef,
+// u, the backward saves and the mask are neither addressed nor written, the cost (COST = true
+// arithmetic), x_N, tau and the step count leave once per path after the time loop, and every
+// descriptor covers only the workgroup's own rows of a [B][d] array (so no array is addressed
+// through an [N+1]-slab descriptor, and kOOB stays out of range whatever B is).  kNnLeanPhilox
+// also reads no dw: each step lane draws its increments, the stream of dpac_sample.
+enum NnMode : int { kNnFull = 0, kNnLeanDw = 1, kNnLeanPhilox = 2 };
+
+// The lean modes' per-lane state: the in-kernel draw (what k_rollout's PHILOX load does: in the
+// paired layout the even step of a pair draws both steps' increments and the odd step takes the
+// half kept in pend; loads come in step order, pipelined()) and the tau / step-count sums.
+// The draw is pinned where the load functor stands: its rounds start after the previous step's
+// stores and its values are in registers before the barrier that opens the next MLP, so they
+// neither spread into the MLP's register peak nor wait behind it.
+template <typename T, class E, int D, int MODE>
+struct NnLean {
+  static constexpr int P = E::kP, M = E::M;
+  static constexpr bool kPairable = MODE == kNnLeanPhilox && P > 1 && 2 * M <= 4;
+  // float64 draws where the step uses them, after the MLP: rocRAND's double Box-Muller on top of
+  // the registers live across the load point spills (12 to 24 bytes of scratch, measured); float
+  // draws in the load functor, a step ahead
+  static constexpr bool kDrawAtUse = sizeof(T) == 8;
+  bool paired;
+  T pend[kPairable ? M : 1];
+  T tau;
+  int steps;
+  __device__ __forceinline__ NnLean(const NnRolloutArgs<T>& a, int64_t)
+      : paired(kPairable && dw_steps_per_block<T>(M, a.sample_type) == 2), tau(0), steps(0) {
+#pragma unroll
+    for (int m = 0; m < (kPairable ? M : 1); ++m) pend[m] = T(0);
+  }
+  // One-lane groups (VDP): every slot of the stream's own lane split, in component order.  In
+  // the paired layout the block's values are pinned into registers before this step's half is
+  // taken (a select between two elements of the block array would index it at run time and
+  // keep it in memory).
+  __device__ __forceinline__ static void draw_row(uint64_t seed, uint64_t traj, int t, int st, T (&out)[M]) {
+    constexpr int PR = lanes_for_dim(D), MR = comps_per_lane(D);
+    const bool odd = (t & 1) != 0;
+#pragma unroll
+    for (int p = 0; p < PR; ++p) {
+      if (p * MR >= D) continue;
+      T s[MR];
+      bool done = false;
+      if constexpr (2 * MR <= 4) {
+        if (dw_steps_per_block<T>(MR, st) == 2) {
+          T v[2 * MR];
+          draw_slot_pair<T, D>(seed, traj, t >> 1, p, st, v);
+#pragma unroll
+          for (int i = 0; i < 2 * MR; ++i) pin(v[i]);
+#pragma unroll
+          for (int m = 0; m < MR; ++m) s[m] = odd ? v[MR + m] : v[m];
+          done = true;
+        }
+      }
+      if (!done) draw_slot_single<T, D>(seed, traj, t, p, st, s);
+#pragma unroll
+      for (int m = 0; m < MR; ++m)
+        if (p * MR + m < D) out[p * MR + m] = s[m];
+    }
+  }
+  // the increments of step t of trajectory b's lane slot p, zero in the slots past d (as a dw row reads)
+  __device__ __forceinline__ void draw(const NnRolloutArgs<T>& a, const Own<D, P>& own, int64_t b, int t,
+                                       T (&dw)[M]) {
+    pin(t);  // the rounds start here
+    const uint64_t gtraj = (uint64_t)(a.traj_offset + b);
+    if constexpr (P == 1) {
+      static_assert(M == D, "one lane holds the whole row");
+      draw_row(a.seed, gtraj, t, a.sample_type, dw);
+    } else {
+      static_assert(lanes_for_dim(D) == P && comps_per_lane(D) == M, "RNG slots follow the lane split");
+      bool done = false;
+      if constexpr (kPairable) {
+        if (paired) {
+          if ((t & 1) == 0) {
+            T v[2 * M];
+            draw_slot_pair<T, D>(a.seed, gtraj, t >> 1, own.p, a.sample_type, v);
+#pragma unroll
+            for (int m = 0; m < M; ++m) {
+              dw[m] = v[m];
+              pend[m] = v[M + m];
+            }
+          } else {
+#pragma unroll
+            for (int m = 0; m < M; ++m) dw[m] = pend[m];
+          }
+          done = true;
+        }
+      }
+      if (!done) draw_slot_single<T, D>(a.seed, gtraj, t, own.p, a.sample_type, dw);
+    }
+    own.mask(dw);
+#pragma unroll
+    for (int m = 0; m < M; ++m) pin(dw[m]);  // and end here, ahead of the barrier
+    if constexpr (kPairable) {
+#pragma unroll
+      for (int m = 0; m < M; ++m) pin(pend[m]);
+    }
+  }
+  __device__ __forceinline__ void count(bool coef, T cf, T dt) {
+    tau += cf * dt;
+    steps += coef ? 1 : 0;
+  }
+  // tau and the step count of trajectory b (its first lane, a live row)
+  __device__ __forceinline__ void store(const NnRolloutArgs<T>& a, int64_t b) const {
+    if (a.tau) a.tau[b] = tau;
+    if (a.steps) a.steps[b] = steps;
+  }
+};
+template <typename T, class E, int D>
+struct NnLean<T, E, D, kNnFull> {  // today's kernels keep none of it
+  __device__ __forceinline__ NnLean(const NnRolloutArgs<T>&, int64_t) {}
+};
+
+// The dw [N][B][d] descriptor of a workgroup whose first row is row0 (slab = one step's bytes):
+// the whole array; in kNnLeanDw from row0 on (the lean modes' row offsets start there; the host
+// keeps N * slab below 2 GiB where dw is read); none in kNnLeanPhilox.
+template <typename T, int D, int MODE>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t nn_dw_rsrc(const NnRolloutArgs<T>& a, int64_t row0,
+                                                             uint32_t slab) {
+  if constexpr (MODE == kNnLeanPhilox) return make_rsrc(nullptr, 0u);
+  else if constexpr (MODE == kNnLeanDw)
+    return make_rsrc(a.dw + row0 * D, slab * (uint32_t)a.N - (uint32_t)(row0 * D * (int64_t)sizeof(T)));
+  else return make_rsrc(a.dw, slab * (uint32_t)a.N);
+}
 
 // out[16 x Nout] = in[16 x K] @ W[K x Nout] for the workgroup's 16 rows, this
 // wave's NT 16-column tiles (wave, wave + 4, ...), followed by a per-element
@@ -921,11 +1053,14 @@ __global__ __launch_bounds__(kNnThreads) void k_rollout_nn_bwd(const E eq, const
   if (a.g_x0 && live) own.store(a.g_x0 + lc.b * D, lam);
 }
 
-template <typename T, class E, int D, int SCHEME, bool COST, int KB, bool FAST, bool MASK = false>
+template <typename T, class E, int D, int SCHEME, bool COST, int KB, bool FAST, bool MASK = false,
+          int MODE = kNnFull>
 __global__ __launch_bounds__(kNnThreads) void k_rollout_nn(const E eq, const DevConsts<T> c,
                                                           const NnMlp<T> mlp,
                                                           const NnRolloutArgs<T> a) {
   constexpr int P = E::kP, M = E::M, MC = E::MC;
+  constexpr bool LEAN = MODE != kNnFull;
+  static_assert(!LEAN || (COST && !MASK), "the lean modes: the cost, no saves, no mask");
   using TR = Transition<T, E, SCHEME>;
   __shared__ T s_x0[kNnRows * kNnLd];   // BN_0(x_t)
   __shared__ T s_pq[2][kNnRows * kNnLd];
@@ -941,13 +1076,15 @@ __global__ __launch_bounds__(kNnThreads) void k_rollout_nn(const E eq, const Dev
   const bool live = stepper && lc.live;
   const Own<D, P> own(lc.p);
   const Own<E::CDIM, P> ownu(lc.p);
-  const BufSlab<T, D, P> sx(own, lc.b, live);
+  const BufSlab<T, D, P> sx(own, LEAN ? lc.b - row0 : lc.b, live);  // lean: from the workgroup's first row
   const BufSlab<T, E::CDIM, P> su(ownu, lc.b, live);
   const uint32_t slab = (uint32_t)(a.B * D * sizeof(T));
   const uint32_t slab_u = (uint32_t)(a.B * E::CDIM * sizeof(T));
-  const __amdgpu_buffer_rsrc_t rs_x = make_rsrc(a.x, slab * (uint32_t)(a.N + 1));
-  const __amdgpu_buffer_rsrc_t rs_dw = make_rsrc(a.dw, slab * (uint32_t)a.N);
-  const __amdgpu_buffer_rsrc_t rs_u = make_rsrc(a.u, a.u ? slab_u * (uint32_t)a.N : 0u);
+  const __amdgpu_buffer_rsrc_t rs_x = LEAN ? rows_rsrc(a.x_end, row0, rows_live, D)
+                                           : make_rsrc(a.x, slab * (uint32_t)(a.N + 1));
+  const __amdgpu_buffer_rsrc_t rs_dw = nn_dw_rsrc<T, D, MODE>(a, row0, slab);
+  const __amdgpu_buffer_rsrc_t rs_u = make_rsrc(LEAN ? nullptr : a.u, !LEAN && a.u ? slab_u * (uint32_t)a.N : 0u);
+  NnLean<T, E, D, MODE> lean(a, lc.b);
   const int L = mlp.L, c_out = mlp.width[L + 1];
 
   // zero padding: A columns past K (up to a prefetch ring beyond) read zeros
@@ -973,8 +1110,8 @@ __global__ __launch_bounds__(kNnThreads) void k_rollout_nn(const E eq, const Dev
   };
 
   T x[M];
-  sx.load(make_rsrc(a.x0, slab), x);
-  sx.store(rs_x, x);
+  sx.load(LEAN ? rows_rsrc(a.x0, row0, rows_live, D) : make_rsrc(a.x0, slab), x);
+  if constexpr (!LEAN) sx.store(rs_x, x);
   T r = TR::kRadius ? dsqrt(Lanes<P>::sum(sumsq(x))) : T(0);
   Flags fl = SCHEME == DPAC_SCHEME_ADAPTIVE ? region(r, c) : Flags{true, false};
   T disc = 1, y = 0;
@@ -990,7 +1127,10 @@ __global__ __launch_bounds__(kNnThreads) void k_rollout_nn(const E eq, const Dev
   __syncthreads();  // padding zeroed before the first a0 write
   write_a0(x);
 
-  auto load = [&](int t, DwFrame<T, M>& fr) { sx.load(rs_dw, fr.dw, (uint32_t)t * slab); };
+  auto load = [&](int t, DwFrame<T, M>& fr) {
+    if constexpr (MODE != kNnLeanPhilox) sx.load(rs_dw, fr.dw, (uint32_t)t * slab);
+    else if constexpr (!NnLean<T, E, D, MODE>::kDrawAtUse) lean.draw(a, own, lc.b, t, fr.dw);
+  };
   auto body = [&](int t, DwFrame<T, M>& fr, auto) {
     __syncthreads();  // a0 of step t is in s_x0; the previous step's reads are done
     NN_MARK(t, 0);
@@ -1000,7 +1140,7 @@ __global__ __launch_bounds__(kNnThreads) void k_rollout_nn(const E eq, const Dev
     for (int l = 0; l <= L; ++l) {
       T* out = s_pq[pq];
       FwdEpi<T> epi{mlp.scale[l + 1], mlp.shift[l + 1], l == L ? mlp.bias : nullptr, l < L, out,
-                    a.save_z ? a.save_z + ((int64_t)t * a.B + row0) * mlp.ztot + mlp.zoff[l + 1] : nullptr,
+                    !LEAN && a.save_z ? a.save_z + ((int64_t)t * a.B + row0) * mlp.ztot + mlp.zoff[l + 1] : nullptr,
                     mlp.ztot, rows_live};
       if constexpr (FAST) {
         if (MASK && l < L) {  // hidden output with its sign bits
@@ -1048,9 +1188,14 @@ __global__ __launch_bounds__(kNnThreads) void k_rollout_nn(const E eq, const Dev
 #pragma unroll
       for (int m = 0; m < MC; ++m) u[m] = u[m] / den;
     }
-    if (a.save_flag && lc.p == 0 && live) {
-      a.save_flag[(int64_t)t * a.B + lc.b] = fl.encode();
-      a.save_disc[(int64_t)t * a.B + lc.b] = disc;
+    if constexpr (!LEAN) {
+      if (a.save_flag && lc.p == 0 && live) {
+        a.save_flag[(int64_t)t * a.B + lc.b] = fl.encode();
+        a.save_disc[(int64_t)t * a.B + lc.b] = disc;
+      }
+    }
+    if constexpr (MODE == kNnLeanPhilox) {
+      if constexpr (NnLean<T, E, D, MODE>::kDrawAtUse) lean.draw(a, own, lc.b, t, fr.dw);
     }
     T dwv[M];
 #pragma unroll
@@ -1067,16 +1212,24 @@ __global__ __launch_bounds__(kNnThreads) void k_rollout_nn(const E eq, const Dev
     for (int m = 0; m < M; ++m) x[m] = tr.coef ? tr.xt[m] : x[m];
     if constexpr (TR::kRadius) r = tr.coef ? tr.rt : r;
     fl = tr.next;
-    sx.store(rs_x, x, (uint32_t)(t + 1) * slab);
-    if (a.u) su.store(rs_u, u, (uint32_t)t * slab_u);
-    if (lc.p == 0 && live) {
-      a.dt[lc.b * a.N + t] = tr.dt;
-      a.coef[lc.b * a.N + t] = cf;
+    if constexpr (LEAN) {
+      lean.count(tr.coef, cf, tr.dt);
+    } else {
+      sx.store(rs_x, x, (uint32_t)(t + 1) * slab);
+      if (a.u) su.store(rs_u, u, (uint32_t)t * slab_u);
+      if (lc.p == 0 && live) {
+        a.dt[lc.b * a.N + t] = tr.dt;
+        a.coef[lc.b * a.N + t] = cf;
+      }
     }
     write_a0(x);
     NN_MARK(t, 15);
   };
   pipelined<KB, DwFrame<T, M>>(0, a.N, load, body);
+  if constexpr (LEAN) {
+    sx.store(rs_x, x);  // x_N
+    if (live && lc.p == 0) lean.store(a, lc.b);
+  }
   if constexpr (COST) {
     if (live && lc.p == 0) {
       a.y[lc.b] = y;

@@ -152,13 +152,15 @@ __device__ __forceinline__ void n4_epilogue(const float* part, int H, int tid, E
   }
 }
 
-template <typename T, class E, int D, int SCHEME, bool COST, int RG>
+template <typename T, class E, int D, int SCHEME, bool COST, int RG, int MODE = kNnFull>
 __global__ __launch_bounds__(kN4Threads) void k_rollout_nn4(const E eq, const DevConsts<T> c,
                                                            const NnMlp<T> mlp,
                                                            const NnRolloutArgs<T> a) {
   static_assert(std::is_same<T, float>::value, "4x4x1 MFMA path is float only");
   constexpr int P = E::kP, M = E::M, MC = E::MC, ROWS = 4 * RG;
   static_assert(ROWS * P <= kN4Threads, "step lanes fit the workgroup");
+  constexpr bool LEAN = MODE != kNnFull;  // NnMode (dpac_rollout_nn.h)
+  static_assert(!LEAN || COST, "the lean modes come with the cost");
   using TR = Transition<T, E, SCHEME>;
   __shared__ __attribute__((aligned(16))) float s_x0[ROWS * kN4Ld];      // BN_0(x_t)
   __shared__ __attribute__((aligned(16))) float s_img[2][ROWS * kN4Ld];  // layer outputs
@@ -174,13 +176,15 @@ __global__ __launch_bounds__(kN4Threads) void k_rollout_nn4(const E eq, const De
   const bool live = stepper && lc.live;
   const Own<D, P> own(lc.p);
   const Own<E::CDIM, P> ownu(lc.p);
-  const BufSlab<T, D, P> sx(own, lc.b, live);
+  const BufSlab<T, D, P> sx(own, LEAN ? lc.b - row0 : lc.b, live);  // lean: from the workgroup's first row
   const BufSlab<T, E::CDIM, P> su(ownu, lc.b, live);
   const uint32_t slab = (uint32_t)(a.B * D * sizeof(T));
   const uint32_t slab_u = (uint32_t)(a.B * E::CDIM * sizeof(T));
-  const __amdgpu_buffer_rsrc_t rs_x = make_rsrc(a.x, slab * (uint32_t)(a.N + 1));
-  const __amdgpu_buffer_rsrc_t rs_dw = make_rsrc(a.dw, slab * (uint32_t)a.N);
-  const __amdgpu_buffer_rsrc_t rs_u = make_rsrc(a.u, a.u ? slab_u * (uint32_t)a.N : 0u);
+  const __amdgpu_buffer_rsrc_t rs_x = LEAN ? rows_rsrc(a.x_end, row0, rows_live, D)
+                                           : make_rsrc(a.x, slab * (uint32_t)(a.N + 1));
+  const __amdgpu_buffer_rsrc_t rs_dw = nn_dw_rsrc<T, D, MODE>(a, row0, slab);
+  const __amdgpu_buffer_rsrc_t rs_u = make_rsrc(LEAN ? nullptr : a.u, !LEAN && a.u ? slab_u * (uint32_t)a.N : 0u);
+  NnLean<T, E, D, MODE> lean(a, lc.b);
   const int L = mlp.L, c_out = mlp.width[L + 1];
   // BN scale / shift of every dense layer's output (and the output bias) in LDS
   for (int l = 0; l <= L; ++l)
@@ -206,14 +210,17 @@ __global__ __launch_bounds__(kN4Threads) void k_rollout_nn4(const E eq, const De
   };
 
   T x[M];
-  sx.load(make_rsrc(a.x0, slab), x);
-  sx.store(rs_x, x);
+  sx.load(LEAN ? rows_rsrc(a.x0, row0, rows_live, D) : make_rsrc(a.x0, slab), x);
+  if constexpr (!LEAN) sx.store(rs_x, x);
   T r = TR::kRadius ? dsqrt(Lanes<P>::sum(sumsq(x))) : T(0);
   Flags fl = SCHEME == DPAC_SCHEME_ADAPTIVE ? region(r, c) : Flags{true, false};
   T disc = 1, y = 0;
   write_a0(x);
 
-  auto load = [&](int t, DwFrame<T, M>& fr) { sx.load(rs_dw, fr.dw, (uint32_t)t * slab); };
+  auto load = [&](int t, DwFrame<T, M>& fr) {
+    if constexpr (MODE == kNnLeanPhilox) lean.draw(a, own, lc.b, t, fr.dw);
+    else sx.load(rs_dw, fr.dw, (uint32_t)t * slab);
+  };
   auto body = [&](int t, DwFrame<T, M>& fr, auto) {
     __syncthreads();  // a0 of step t is in s_x0; the previous step's reads are done
     // ---- actor MLP (all eight wavefronts) ----
@@ -228,7 +235,7 @@ __global__ __launch_bounds__(kN4Threads) void k_rollout_nn4(const E eq, const De
       const float* sh = s_bn[l][1];
       const float* bi = s_bn[l][2];
       const bool hidden = l < L;
-      T* save = a.save_z ? a.save_z + ((int64_t)t * a.B + row0) * mlp.ztot + mlp.zoff[l + 1] : nullptr;
+      T* save = !LEAN && a.save_z ? a.save_z + ((int64_t)t * a.B + row0) * mlp.ztot + mlp.zoff[l + 1] : nullptr;
       n4_epilogue<RG>(s_part, H, tid, [&](int rr, int c0, const float (&z)[4]) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -258,9 +265,11 @@ __global__ __launch_bounds__(kN4Threads) void k_rollout_nn4(const E eq, const De
 #pragma unroll
       for (int m = 0; m < MC; ++m) u[m] = u[m] / den;
     }
-    if (a.save_flag && lc.p == 0 && live) {
-      a.save_flag[(int64_t)t * a.B + lc.b] = fl.encode();
-      a.save_disc[(int64_t)t * a.B + lc.b] = disc;
+    if constexpr (!LEAN) {
+      if (a.save_flag && lc.p == 0 && live) {
+        a.save_flag[(int64_t)t * a.B + lc.b] = fl.encode();
+        a.save_disc[(int64_t)t * a.B + lc.b] = disc;
+      }
     }
     T dwv[M];
 #pragma unroll
@@ -277,15 +286,23 @@ __global__ __launch_bounds__(kN4Threads) void k_rollout_nn4(const E eq, const De
     for (int m = 0; m < M; ++m) x[m] = tr.coef ? tr.xt[m] : x[m];
     if constexpr (TR::kRadius) r = tr.coef ? tr.rt : r;
     fl = tr.next;
-    sx.store(rs_x, x, (uint32_t)(t + 1) * slab);
-    if (a.u) su.store(rs_u, u, (uint32_t)t * slab_u);
-    if (lc.p == 0 && live) {
-      a.dt[lc.b * a.N + t] = tr.dt;
-      a.coef[lc.b * a.N + t] = cf;
+    if constexpr (LEAN) {
+      lean.count(tr.coef, cf, tr.dt);
+    } else {
+      sx.store(rs_x, x, (uint32_t)(t + 1) * slab);
+      if (a.u) su.store(rs_u, u, (uint32_t)t * slab_u);
+      if (lc.p == 0 && live) {
+        a.dt[lc.b * a.N + t] = tr.dt;
+        a.coef[lc.b * a.N + t] = cf;
+      }
     }
     write_a0(x);
   };
   pipelined<1, DwFrame<T, M>>(0, a.N, load, body);
+  if constexpr (LEAN) {
+    sx.store(rs_x, x);  // x_N
+    if (live && lc.p == 0) lean.store(a, lc.b);
+  }
   if constexpr (COST) {
     if (live && lc.p == 0) {
       a.y[lc.b] = y;

@@ -412,12 +412,14 @@ __device__ __forceinline__ float nx_group_max(float v) {
 // ---------------------------------------------------------------------------
 // Forward: k_rollout_nn's step with the MLP on split-fp16 MFMA.
 // ---------------------------------------------------------------------------
-template <class E, int D, int SCHEME, bool COST, bool SAVE, bool MASK>
+template <class E, int D, int SCHEME, bool COST, bool SAVE, bool MASK, int MODE = kNnFull>
 __global__ __launch_bounds__(kNnThreads) void k_rollout_nn_x3(const E eq, const DevConsts<float> c,
                                                              const NnMlp<float> mlp,
                                                              const NnRolloutArgs<float> a) {
   using T = float;
   constexpr int P = E::kP, M = E::M, MC = E::MC, CD = E::CDIM;
+  constexpr bool LEAN = MODE != kNnFull;  // NnMode (dpac_rollout_nn.h)
+  static_assert(!LEAN || (COST && !SAVE && !MASK), "the lean modes: the cost, no saves, no mask");
   using TR = Transition<T, E, SCHEME>;
   extern __shared__ __attribute__((aligned(16))) unsigned char nx_lds[];
   _Float16* const img0 = reinterpret_cast<_Float16*>(nx_lds + NxLds::img0);
@@ -443,13 +445,15 @@ __global__ __launch_bounds__(kNnThreads) void k_rollout_nn_x3(const E eq, const 
   const bool live = stepper && lc.live;
   const Own<D, P> own(lc.p);
   const Own<CD, P> ownu(lc.p);
-  const BufSlab<T, D, P> sx(own, lc.b, live);
+  const BufSlab<T, D, P> sx(own, LEAN ? lc.b - row0 : lc.b, live);  // lean: from the workgroup's first row
   const BufSlab<T, CD, P> su(ownu, lc.b, live);
   const uint32_t slab = (uint32_t)(a.B * D * sizeof(T));
   const uint32_t slab_u = (uint32_t)(a.B * CD * sizeof(T));
-  const __amdgpu_buffer_rsrc_t rs_x = make_rsrc(a.x, slab * (uint32_t)(a.N + 1));
-  const __amdgpu_buffer_rsrc_t rs_dw = make_rsrc(a.dw, slab * (uint32_t)a.N);
-  const __amdgpu_buffer_rsrc_t rs_u = make_rsrc(a.u, a.u ? slab_u * (uint32_t)a.N : 0u);
+  const __amdgpu_buffer_rsrc_t rs_x = LEAN ? rows_rsrc(a.x_end, row0, rows_live, D)
+                                           : make_rsrc(a.x, slab * (uint32_t)(a.N + 1));
+  const __amdgpu_buffer_rsrc_t rs_dw = nn_dw_rsrc<T, D, MODE>(a, row0, slab);
+  const __amdgpu_buffer_rsrc_t rs_u = make_rsrc(LEAN ? nullptr : a.u, !LEAN && a.u ? slab_u * (uint32_t)a.N : 0u);
+  NnLean<T, E, D, MODE> lean(a, lc.b);
   const int L = mlp.L, c_out = mlp.width[L + 1];
   const int nch_out = (mlp.width[L] + 31) / 32;  // 32-k chunks of the output layer's weight image
   constexpr int nparts = kNnWaves;  // split-K partials the step lanes add: one per wave (nx_fold_prod)
@@ -497,15 +501,18 @@ __global__ __launch_bounds__(kNnThreads) void k_rollout_nn_x3(const E eq, const 
     }
   };
   T x[M];
-  sx.load(make_rsrc(a.x0, slab), x);
-  sx.store(rs_x, x);
+  sx.load(LEAN ? rows_rsrc(a.x0, row0, rows_live, D) : make_rsrc(a.x0, slab), x);
+  if constexpr (!LEAN) sx.store(rs_x, x);
   T r = TR::kRadius ? dsqrt(Lanes<P>::sum(sumsq(x))) : T(0);
   Flags fl = SCHEME == DPAC_SCHEME_ADAPTIVE ? region(r, c) : Flags{true, false};
   T disc = 1, y = 0;
   __syncthreads();  // LDS zeroed before the first a0 write
   write_a0(x);
 
-  auto load = [&](int t, DwFrame<T, M>& fr) { sx.load(rs_dw, fr.dw, (uint32_t)t * slab); };
+  auto load = [&](int t, DwFrame<T, M>& fr) {
+    if constexpr (MODE == kNnLeanPhilox) lean.draw(a, own, lc.b, t, fr.dw);
+    else sx.load(rs_dw, fr.dw, (uint32_t)t * slab);
+  };
   auto body = [&](int t, DwFrame<T, M>& fr, auto) {
     __syncthreads();  // a0 of step t is in in0; the previous step's partial reads are done
     NN_MARK(t, 0);
@@ -575,9 +582,11 @@ __global__ __launch_bounds__(kNnThreads) void k_rollout_nn_x3(const E eq, const 
 #pragma unroll
       for (int m = 0; m < MC; ++m) u[m] = u[m] / den;
     }
-    if (a.save_flag && lc.p == 0 && live) {
-      a.save_flag[(int64_t)t * a.B + lc.b] = fl.encode();
-      a.save_disc[(int64_t)t * a.B + lc.b] = disc;
+    if constexpr (!LEAN) {
+      if (a.save_flag && lc.p == 0 && live) {
+        a.save_flag[(int64_t)t * a.B + lc.b] = fl.encode();
+        a.save_disc[(int64_t)t * a.B + lc.b] = disc;
+      }
     }
     T dwv[M];
 #pragma unroll
@@ -594,16 +603,24 @@ __global__ __launch_bounds__(kNnThreads) void k_rollout_nn_x3(const E eq, const 
     for (int m = 0; m < M; ++m) x[m] = tr.coef ? tr.xt[m] : x[m];
     if constexpr (TR::kRadius) r = tr.coef ? tr.rt : r;
     fl = tr.next;
-    sx.store(rs_x, x, (uint32_t)(t + 1) * slab);
-    if (a.u) su.store(rs_u, u, (uint32_t)t * slab_u);
-    if (lc.p == 0 && live) {
-      a.dt[lc.b * a.N + t] = tr.dt;
-      a.coef[lc.b * a.N + t] = cf;
+    if constexpr (LEAN) {
+      lean.count(tr.coef, cf, tr.dt);
+    } else {
+      sx.store(rs_x, x, (uint32_t)(t + 1) * slab);
+      if (a.u) su.store(rs_u, u, (uint32_t)t * slab_u);
+      if (lc.p == 0 && live) {
+        a.dt[lc.b * a.N + t] = tr.dt;
+        a.coef[lc.b * a.N + t] = cf;
+      }
     }
     write_a0(x);
     NN_MARK(t, 15);
   };
   pipelined<1, DwFrame<T, M>>(0, a.N, load, body);
+  if constexpr (LEAN) {
+    sx.store(rs_x, x);  // x_N
+    if (live && lc.p == 0) lean.store(a, lc.b);
+  }
   if constexpr (COST) {
     if (live && lc.p == 0) {
       a.y[lc.b] = y;

@@ -36,6 +36,16 @@ class TrajectoryBatch(NamedTuple):
     x_bdry: torch.Tensor
 
 
+class PolicyCost(NamedTuple):
+    """Per-path results of Equation.policy_cost: y [B] the running cost (actor order), disc [B]
+    the discount at the end, x_end [B,d], tau [B] the time run, steps [B] int32 the steps taken."""
+    y: torch.Tensor
+    disc: torch.Tensor
+    x_end: torch.Tensor
+    tau: torch.Tensor
+    steps: torch.Tensor
+
+
 def _device():
     if not torch.cuda.is_available():
         raise _lib.DpacUnavailable("no ROCm GPU visible: the libdpac hot path has no CPU fallback")
@@ -152,6 +162,20 @@ class Equation(object):
             x, dt, coef, u, _, _, _ = ops.rollout_nn(eqp, sch, x0, dw, T, N, NN_control.mlp_view())
             return x, dt, coef, u
         return rollout_nn_nograd(eqp, sch, x0, dw, T, N, NN_control)
+
+    def policy_cost(self, scheme: str, x0, T: float, N: int, NN_control, *, dw=None, seed: int = 0,
+                    traj_offset: int = 0, kind: str = "normal") -> PolicyCost:
+        """The cost of the policy NN_control from the states x0 [B,d], one path each, in one
+        launch that keeps no trajectory (dpac_policy_cost): per path the running cost, the final
+        discount and state, the time run and the steps taken.  dw [N,B,d], or None: path b
+        draws its increments in-kernel, those of sample_device(kind, ..., seed, traj_offset)[b].
+        The network runs inside the kernel: there is no per-step fallback for this call."""
+        if not (hasattr(NN_control, "fused_ok") and NN_control.fused_ok()):
+            raise ValueError("policy_cost needs a network the fused rollout serves (at most "
+                             f"{_lib.MLP_MAX_HIDDEN} hidden layers of at most {_lib.MLP_MAX_WIDTH} units)")
+        return PolicyCost(*ops.policy_cost(self.params(), SCHEMES[scheme], x0, dw, T, N, NN_control.mlp_view(),
+                                           seed=seed, traj_offset=traj_offset, sample_type=SAMPLE_TYPES[kind],
+                                           want_tau=True, want_steps=True))
 
     def _propagate(self, scheme, num_sample, x0, dw_sample, NN_control, training, T, N, cheat):
         x0 = _as_dev(x0).contiguous()

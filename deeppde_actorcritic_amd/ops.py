@@ -355,6 +355,34 @@ def rollout_nn(eqp, scheme: int, x0: torch.Tensor, dw: torch.Tensor, total_time:
     return x, dt, coef, u, y, disc, saves
 
 
+def policy_cost(eqp, scheme: int, x0: torch.Tensor, dw: torch.Tensor | None, total_time: float,
+                num_steps: int, mlp: MlpView, *, seed: int = 0, traj_offset: int = 0,
+                sample_type: int = _lib.SAMPLE_NORMAL, cost_order: int = _lib.COST_ACTOR,
+                want_tau: bool = False, want_steps: bool = False):
+    """Policy evaluation: rollout_nn's rollout without its trajectory arrays, one launch of
+    dpac_policy_cost (include/dpac.h).
+
+    Returns (y [B], disc [B], x_end [B,d], tau [B] | None, steps [B] int32 | None): the pathwise
+    cost in `cost_order`, the state after step N, tau = sum of coef*dt and steps = sum of coef,
+    bitwise rollout_nn's for the same dw.  dw=None draws the increments in-kernel from the Philox
+    stream of sample(seed=seed, traj_offset=traj_offset): no [N, B, d] array exists at all."""
+    _require_gpu(x0, dw, *mlp.tensors)
+    _check_same(x0, dw, *mlp.tensors)
+    B, d = x0.shape
+    N = num_steps
+    if dw is not None and tuple(dw.shape) != (N, B, d):
+        raise ValueError(f"dw must be [N, B, d] = {(N, B, d)}, got {tuple(dw.shape)}")
+    kw = dict(dtype=x0.dtype, device=x0.device)
+    y, disc, x_end = torch.empty(B, **kw), torch.empty(B, **kw), torch.empty(B, d, **kw)
+    tau = torch.empty(B, **kw) if want_tau else None
+    steps = torch.empty(B, dtype=torch.int32, device=x0.device) if want_steps else None
+    call("dpac_policy_cost", ctypes.byref(eqp), scheme, _dtype_id(x0), B, N, float(total_time),
+         ctypes.byref(mlp.struct), _ptr(x0.contiguous()), _ptr(None if dw is None else dw.contiguous()),
+         _u64(seed), traj_offset, sample_type, cost_order, _ptr(y), _ptr(disc), _ptr(x_end), _ptr(tau),
+         _ptr(steps), _stream(x0))
+    return y, disc, x_end, tau, steps
+
+
 def _split_params(params):
     """(L, gamma[L+2], beta[L+2], W[L+1], b) of DeepNN.trainable_variables()."""
     L = (len(params) - 1) // 3 - 1

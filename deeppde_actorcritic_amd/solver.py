@@ -21,6 +21,7 @@ import contextlib
 import logging
 import os
 import time
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -235,6 +236,17 @@ class ActorModel(nn.Module):
         return (y + term * disc).unsqueeze(1)  # solver.py:220-223
 
 
+class PolicyEvaluation(NamedTuple):
+    """ActorCriticSolver.evaluate_policy: per start point (float64 [S]) the Monte-Carlo cost of
+    the actor's policy, its standard error, the fraction of paths that stopped early and the mean
+    time run; num_paths paths each."""
+    cost: torch.Tensor
+    stderr: torch.Tensor
+    exit_frac: torch.Tensor
+    mean_tau: torch.Tensor
+    num_paths: int
+
+
 # ---------------------------------------------------------------------------
 # The DPAC_* knobs: read here and nowhere else (optim and step_graphs get what they decide as
 # arguments), when a solver builds an optimizer or a graph set, so a test can patch them here
@@ -370,6 +382,7 @@ class ActorCriticSolver(object):
         self.cheat_control_in_critic = self.train_config.train == "critic"
         self.cheat_value_in_actor = self.train_config.train == "actor"
         self._calls = 0
+        self._eval_calls = 0  # evaluate_policy's own key count (not part of state_dict)
         self._next_samples = None  # (spec, critic batch, actor batch, ready event)
         self._sample_side = None
         self.hip_graphs = (self.sampler == "device") if graphs is None else bool(graphs)
@@ -819,6 +832,69 @@ class ActorCriticSolver(object):
         y0 = self.model_critic.NN_value(data.x0)
         cnt = data.x0.shape[0]
         return self._mean(torch.mean(y - y0), cnt, total or cnt * self.par.world)
+
+    @torch.no_grad()
+    def evaluate_policy(self, x0, num_paths, *, seed=None, terminal="critic", chunk_rows=1 << 20):
+        """Monte-Carlo cost of the actor's policy from the start points x0 [S, d] (numpy or a
+        tensor, the reference layout), num_paths paths each, with the actor's scheme, horizon and
+        step count (train_config.scheme, total_time_actor, num_time_interval_actor).
+
+        Global row g = s * num_paths + k is path k of start point s and trajectory g of the
+        Philox stream keyed by `seed`, so the estimate depends neither on chunk_rows nor on the
+        GPU count.  Rows run in chunks of at most chunk_rows through dpac_policy_cost with
+        in-kernel noise: no trajectory and no increment array exists, a chunk keeps about
+        8 + 2 d values per path.  With data parallelism each rank takes its shard of the rows.
+        The pathwise cost is c = y + term * disc with term = NN_value(x_end) ("critic"),
+        V_true(x_end) ("true") or 0 ("none").  Returns PolicyEvaluation(cost, stderr, exit_frac,
+        mean_tau, num_paths): the mean of c, sqrt(unbiased variance / num_paths) (NaN for one
+        path), the fraction of paths that stopped before the last step (steps < N: a path that
+        leaves the domain during the last step is not counted), and the mean of
+        tau = sum coef * dt.  seed=None takes a fresh key from the solver's seed without
+        touching the training sampler's call count (state_dict() resume stays bit for bit)."""
+        if terminal not in ("critic", "true", "none"):
+            raise ValueError(f"terminal must be 'critic', 'true' or 'none', got {terminal!r}")
+        num_paths, chunk_rows = int(num_paths), int(chunk_rows)
+        if num_paths < 1 or chunk_rows < 1:
+            raise ValueError("num_paths and chunk_rows must be >= 1")
+        actor = self.model_actor.NN_control
+        if not actor.fused_ok():
+            raise ValueError("evaluate_policy needs an actor the fused rollout serves (at most "
+                             f"{_lib.MLP_MAX_HIDDEN} hidden layers of at most {_lib.MLP_MAX_WIDTH} units)")
+        if isinstance(x0, torch.Tensor):
+            x0 = x0.to(device=self.device, dtype=self.dtype)
+        else:
+            x0 = torch.as_tensor(np.asarray(x0), dtype=self.dtype, device=self.device)
+        if x0.dim() != 2 or x0.shape[1] != self.bsde.dim:
+            raise ValueError(f"x0 must be [S, {self.bsde.dim}], got {tuple(x0.shape)}")
+        if seed is None:  # a key stream of its own, apart from sample()'s (seed, _calls) keys
+            self._eval_calls += 1
+            seed = (self.seed * 0x9E3779B1 + (0xE7A1 << 40) + self._eval_calls) & 0xFFFFFFFFFFFFFFFF
+        S = x0.shape[0]
+        N = self.eqn_config.num_time_interval_actor
+        T = self.eqn_config.total_time_actor
+        eqp, view = self.bsde.params(), actor.mlp_view()
+        off, cnt = self.par.shard(S * num_paths)
+        mom = torch.zeros(S, 4, dtype=torch.float64, device=self.device)  # sums of c, c^2, tau, [steps < N]
+        for g0 in range(off, off + cnt, chunk_rows):
+            g1 = min(g0 + chunk_rows, off + cnt)
+            s_of = torch.arange(g0, g1, device=self.device) // num_paths
+            y, disc, x_end, tau, steps = ops.policy_cost(
+                eqp, self.model_actor.scheme, x0[s_of], None, T, N, view, seed=seed, traj_offset=g0,
+                sample_type=SAMPLE_TYPES[self.sample_type], want_tau=True, want_steps=True)
+            if terminal == "critic":
+                c = y + self.model_critic.NN_value(x_end)[:, 0] * disc
+            elif terminal == "true":
+                c = y + ops.v_true(eqp, x_end) * disc
+            else:
+                c = y
+            c = c.double()
+            mom.index_add_(0, s_of, torch.stack([c, c * c, tau.double(), (steps < N).double()], 1))
+        mom = self.par.sum(mom)
+        n = float(num_paths)
+        mean = mom[:, 0] / n
+        var = (mom[:, 1] - mom[:, 0] * mean) / (n - 1) if num_paths > 1 else torch.full_like(mean, float("nan"))
+        return PolicyEvaluation(mean, torch.sqrt(torch.clamp(var, min=0.0) / n), mom[:, 3] / n, mom[:, 2] / n,
+                                num_paths)
 
     @torch.no_grad()
     def _valid_loss_critic(self, data, total):

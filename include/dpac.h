@@ -350,6 +350,25 @@ int dpac_rollout_nn_fwd(const dpac_eqn_params* eq, int32_t scheme, int32_t dtype
                         void* disc, void* save_z, int32_t* save_flag, void* save_disc,
                         uint8_t* save_mask, int32_t* mask_written, void* stream);
 
+/* Policy evaluation: the rollout of dpac_rollout_nn_fwd without its trajectory arrays (an
+ * additive entry point of version 10).  Neither x, dt, coef, u nor any save is addressed; each
+ * path leaves y [B] and disc [B] (the pathwise cost in `cost_order`, the arithmetic of
+ * dpac_rollout_nn_fwd), x_end [B][d] (the state after step N, dpac_rollout_nn_fwd's x[N]), and,
+ * each optional (NULL = not written), tau [B] = Σ_t coef_t dt_t (added step by step in `dtype`)
+ * and steps [B] = Σ_t coef_t (int32: the steps taken before the path stopped).  Every output is
+ * bitwise what dpac_rollout_nn_fwd gives for the same x0, dw and actor, on the same kernel
+ * (chosen by dtype, num_sample and the actor's images exactly as there; the range guard and
+ * guard_phase act as there, and the guarded exact-f32 launch rewrites every output).
+ * dw [N][B][d], or NULL: the increments are drawn in-kernel from the Philox stream, bitwise those
+ * of dpac_sample(seed, traj_offset, sample_type); seed, traj_offset and sample_type are read
+ * only then (as dpac_rollout_fwd).  Limits of one launch: a [B][d] array below 4 GiB, and dw,
+ * where given, below 2 GiB; a batch beyond is split over launches with traj_offset. */
+int dpac_policy_cost(const dpac_eqn_params* eq, int32_t scheme, int32_t dtype, int64_t num_sample,
+                     int32_t num_steps, double total_time, const dpac_mlp* actor, const void* x0,
+                     const void* dw, uint64_t seed, int64_t traj_offset, int32_t sample_type,
+                     int32_t cost_order, void* y, void* disc, void* x_end, void* tau, int32_t* steps,
+                     void* stream);
+
 /* The actor's BPTT through a dpac_rollout_nn_fwd rollout (what GradientTape does
  * for solver.py:92-97), as one launch.  Inputs: the forward's x, u, dw and its
  * saves (save_mask: the forward's sign bits where it wrote them, else NULL);
